@@ -340,12 +340,63 @@ def self_launch(args) -> int:
     return rc
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_ENV_SAMPLE = 128       # env columns of the rollout batch kept in the dump (a fixed, seeded subset)
+
+
+def step_outputs(runner, metrics: dict) -> dict:
+    """What the timed path computed in its last step, as float32 / float64 numpy arrays (``--dump-outputs``): the step's metrics
+    (timings left out), the rollout batch with its advantages and returns on a fixed, seeded sample of DUMP_ENV_SAMPLE env
+    columns, and the policy parameters and AdamW moments that the step's optimizer updates left."""
+    import numbers
+
+    import numpy as np
+    w = runner.actor.worker
+    out = {}
+    for k, v in sorted(metrics.items()):
+        if not k.startswith(("time/", "perf/")) and isinstance(v, numbers.Real):
+            out["metric." + k.replace("/", ".")] = np.array([v], dtype=np.float64)
+    batch = w.rollout_batch
+    B = batch["rewards"].shape[1]
+    cols = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:DUMP_ENV_SAMPLE].sort().values
+
+    def host(t: torch.Tensor):
+        t = t.detach().cpu()
+        if t.dim() >= 2 and t.shape[1] == B:
+            t = t[:, cols]
+        return t.double().numpy() if t.dtype in (torch.float64, torch.int64, torch.int32) else t.float().numpy()
+
+    def add(prefix: str, d: dict):
+        for k, v in sorted(d.items()):
+            if isinstance(v, dict):
+                add(f"{prefix}{k}.", v)
+            elif torch.is_tensor(v):
+                out[prefix + k] = host(v)
+
+    add("rollout.", batch)
+    out["params"] = host(w.model.flat)
+    out["exp_avg"], out["exp_avg_sq"] = host(w.exp_avg), host(w.exp_avg_sq)
+    return out
+
+
+def write_outputs(out_dir: str, arrays: dict) -> int:
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def measure(ctx, *, precision: str, scaling: str = "strong", steps: int, warmup: int, use_graph: bool = True,
             pipeline: bool = False, rollout_epochs: int = 1, overlap: bool = False, transport: str | None = None,
-            learner: str = "sync") -> dict:
+            learner: str = "sync", capture: bool = False) -> dict:
     """One timed region: W untimed iterations, then exactly ``steps`` iterations between barrier + synchronize on both sides,
     MAX over ranks.  ``scaling``: strong = 1024 envs / 8192-row global batch in total, weak = that much PER GPU.  Also returns
-    the spread of the iteration time over 10-step windows (host time stamps taken when a window's last step has landed on the host)."""
+    the spread of the iteration time over 10-step windows (host time stamps taken when a window's last step has landed on the host).
+    ``capture``: also return this rank's outputs of the last timed step under "_outputs" (step_outputs, taken after the timed region)."""
     import torch.distributed as dist
     world, dev = ctx.world_size, ctx.device
     envs = ENVS * (world if scaling == "weak" else 1)
@@ -409,6 +460,7 @@ def measure(ctx, *, precision: str, scaling: str = "strong", steps: int, warmup:
             dist.all_gather_object(idents, ident)
             ranks_seen, devices_seen = dist.get_world_size(), len(set(idents))
         xg = w._xgmi
+        outputs = {"_outputs": step_outputs(runner, m)} if capture else {}
         win = sorted((b - a) * 100.0 for a, b in zip(stamps[:-1], stamps[1:]))  # ms per iteration over each 10-step window
         updates = (envs // world * HORIZON // (gb // world)) * UPDATE_EPOCH
         return {"env_steps_per_sec": round(envs * HORIZON * steps / elapsed, 1), "ms_per_step": round(elapsed / steps * 1e3, 3),
@@ -429,7 +481,8 @@ def measure(ctx, *, precision: str, scaling: str = "strong", steps: int, warmup:
                                                   "one_launch_verdict": getattr(xg, "one_launch_verdict", None)}),
                 "metrics_read": "every iteration, one iteration late (runner.defer_metrics)" if DEFER_METRICS else "every iteration, before the next is queued",
                 "last_metrics": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in m.items()
-                                 if k in ("train/actor/total_loss", "train/actor/grad_norm", "train/actor/approx_kl", "rollout/rewards")}}
+                                 if k in ("train/actor/total_loss", "train/actor/grad_norm", "train/actor/approx_kl", "rollout/rewards")},
+                **outputs}
     finally:
         runner.close()
         del runner
@@ -494,6 +547,9 @@ def main():
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) run the CPU baseline and print its object")
     ap.add_argument("--token-cpu-baseline-only", action="store_true", help="(internal) run the token-tier CPU baseline and print its object")
     ap.add_argument("--no-extras", action="store_true", help="skip scaling_model, in_loop_kernels and the exchange probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline run computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: metrics, a fixed sample of the rollout batch, parameters and AdamW moments)")
     ap.add_argument("--exchange", default="none", choices=["none", "self"],
                     help="self (N = 1): only print the measured per-step cost of the gradient exchange's own launches on this device "
                          "(tools/exchange_self.py; also part of scaling_model in the default line)")
@@ -592,8 +648,9 @@ def main():
                 line["transport_errors"] = dict(errors)
         return line
 
+    capture = args.dump_outputs is not None
     if args.gpus == 1:
-        runs[("strong", None)] = measure(ctx, scaling="strong", **common)
+        runs[("strong", None)] = measure(ctx, scaling="strong", capture=capture, **common)
     else:
         # Every (regime, transport) pair is its own runner and its own timed region.  Order: the headline regime first, and inside
         # it the transport most likely to give a number.  A watchdog guards the rest: the N > 1 paths meet real multi-GPU hardware
@@ -624,7 +681,7 @@ def main():
             dog.daemon = True
             dog.start()
             try:
-                runs[(rg, tr)] = measure(ctx, scaling=rg, transport=tr, **common)
+                runs[(rg, tr)] = measure(ctx, scaling=rg, transport=tr, capture=capture and rg == args.scaling, **common)
                 runs[(rg, tr)]["done_at_s"] = round(time.perf_counter() - T_START, 1)  # since this process started
             except Exception as e:  # noqa: BLE001 -- reported in the line; collectively consistent only if it failed everywhere
                 errors[f"{rg}/{tr}"] = f"{type(e).__name__}: {e}"[:300]
@@ -639,6 +696,11 @@ def main():
             raise SystemExit(f"no transport completed the {args.scaling}-scaling run: {errors}")
 
     line = assemble() if ctx.rank == 0 else None
+    if capture and ctx.rank == 0:
+        n = write_outputs(args.dump_outputs, best(args.scaling)[2]["_outputs"])
+        print(f"[bench] --dump-outputs: {n} bytes of the headline run's last step under {args.dump_outputs}", file=sys.stderr)
+    for v in runs.values():
+        v.pop("_outputs", None)
 
     # ---- N = 1: the variant lines (own runners, same timing method), then the probes ---------------------------------------
     if args.gpus == 1:

@@ -48,11 +48,42 @@ def need_dev_variants(what: str):
 
 @pytest.fixture(scope="session")
 def ref():
+    """The reference's hot-path modules: live where the reference tree is readable, else each test's stored calls
+    (tests/helpers/ref_calls.py; RLX_RECORD_REFERENCE=1 records them)."""
+    from helpers import ref_calls
     from oracle import reference_loader
 
-    if not reference_loader.available():
+    live = reference_loader.load() if reference_loader.available() else None
+    return live if (live is not None and not ref_calls.RECORD) else ref_calls.Dispatch(live)
+
+
+@pytest.fixture(autouse=True)
+def _ref_calls(request, monkeypatch):
+    """Points ``ref`` at this test's recording (record / replay); a no-op for tests without ``ref`` and for the live reference."""
+    from helpers import ref_calls
+
+    if "ref" not in request.fixturenames or not isinstance(request.getfixturevalue("ref"), ref_calls.Dispatch):
+        yield
+        return
+    from oracle import reference_loader
+
+    d = request.getfixturevalue("ref")
+    sess = ref_calls.session(request, d.live)
+    if sess is None:
         pytest.skip("reference tree not present on this machine")
-    return reference_loader.load()
+    ref_calls.loader_hooks(sess, reference_loader, monkeypatch)
+    d.current = sess
+    try:
+        yield
+    finally:
+        d.current = None
+    sess.finish()
+
+
+def pytest_sessionfinish(session, exitstatus):
+    from helpers import ref_calls
+
+    ref_calls.write_recordings()
 
 
 def synth_rollout(seed=1234, T=16, B=32, C=1, A=8, D=42, p_done=0.02, device="cpu"):

@@ -17,6 +17,8 @@ class Cfg(dict):
 
 @pytest.fixture(scope="module")
 def registry(ref):
+    if not RL.available():
+        pytest.skip("reference tree not present on this machine")
     mr = RL.load_models_registry()
     reg = ref.registry  # ext.register() also re-registers the advantage / loss callees: everything is put back afterwards
     saved = dict(mr.models._MODEL_REGISTRY), dict(reg.ADV_REGISTRY), dict(reg.LOSS_REGISTRY)

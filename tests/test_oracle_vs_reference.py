@@ -363,7 +363,7 @@ def test_token_actor_loss(ref, agg, zero_first, clip_c):
 
 def test_token_reasoning_shaping(ref):
     b = token_batch(104, 8, 10, 5)
-    values = torch.randn(8, 10)
+    values = torch.randn(8, 10, generator=torch.Generator().manual_seed(104))
     for adv_type in ("gae", "grpo"):
         want = ref.algo_utils.preprocess_reasoning_advantages_inputs(
             rewards=b["rewards"], loss_mask=b["loss_mask"], values=values, adv_type=adv_type, group_size=4)
@@ -607,9 +607,10 @@ def test_async_flatten_rollout_batch(ref):
     fn = reference_loader.load_function("rlinf/workers/actor/async_ppo_fsdp_worker.py", "flatten_rollout_batch_for_train",
                                         torch=torch, Optional=Optional)
     d = synth_rollout(T=6, B=5, C=1)
-    batch = dict(rewards=d["rewards"], dones=d["dones"], prev_values=d["values"], prev_logprobs=torch.randn(6, 5, 8),
+    g = torch.Generator().manual_seed(601)
+    batch = dict(rewards=d["rewards"], dones=d["dones"], prev_values=d["values"], prev_logprobs=torch.randn(6, 5, 8, generator=g),
                  versions=torch.full((6, 5, 8), 3.0), loss_mask=None,
-                 forward_inputs=dict(states=torch.randn(6, 5, 42), action=torch.randn(6, 5, 8)))
+                 forward_inputs=dict(states=torch.randn(6, 5, 42, generator=g), action=torch.randn(6, 5, 8, generator=g)))
     perm = torch.randperm(30, generator=torch.Generator().manual_seed(2))
     want, got = fn(batch, perm), O.flatten_and_shuffle(batch, perm)
     assert set(want) == set(got) and want["loss_mask"] is None and got["loss_mask"] is None
@@ -718,5 +719,5 @@ def test_entropy_bonus_shapes_against_the_reference(ref, etype, C, masked):
         assert float(want) == pytest.approx(float(ent.sum()), rel=1e-6)  # bsz times the mean, whatever the mask holds
     if etype == "chunk_level":
         with pytest.raises(RuntimeError, match="must match the size of tensor"):
-            ref.utils.masked_mean(ref.utils.reshape_entropy(torch.rand(bsz, 3 * A), entropy_type=etype, action_dim=A, batch_size=bsz),
+            ref.utils.masked_mean(ref.utils.reshape_entropy(torch.rand(bsz, 3 * A, generator=g), entropy_type=etype, action_dim=A, batch_size=bsz),
                                   mask=torch.ones(bsz, 3, dtype=torch.bool))
