@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 112 /* 0.1.2: bumped whenever an argument struct or a signature changes (round 6: rlx_xgmi_self_timing, the
+#define RLX_VERSION 113 /* 0.1.3: bumped whenever an argument struct or a signature changes (0.1.3: the OPD entries rlx_opd_*; round 6: rlx_xgmi_self_timing, the
                            * exchange inside rlx_xgmi_clip_adamw_step under sync_words; round 5: rlx_categorical_sample's
                            * softmax_lanes, rlx_adamw_params.sync_words; round 4's struct growth had left it at 100) */
 
@@ -889,6 +889,42 @@ int rlx_xgmi_allreduce_f32(rlx_xgmi_comm* comm, const float* in, int slabs, floa
 int rlx_xgmi_clip_adamw_step(rlx_xgmi_comm* comm, float* params, const float* grads, float* grad_flat, float* exp_avg,
                              float* exp_avg_sq, int64_t n, const rlx_adamw_params* p, float* stats, int32_t* step_state,
                              void* workspace, size_t workspace_bytes, rlx_stream_t stream);
+
+/* a19c  opd  <- compute_opd_advantages rlinf/algorithms/advantages.py:367-407 and compute_opd_actor_loss
+ *        rlinf/algorithms/losses.py:427-505 (registry name "opd" for both; masked_mean / masked_mean_ratio
+ *        rlinf/utils/utils.py:323-356).  Scalars only: no argument struct.
+ *
+ * rlx_opd_advantages: out[t, j] (f32, [rows, inner] contiguous) = float(teacher[t, j]) - float(prev[t, j]) for the first
+ *   `rows` time rows; row t of an input starts at t * <input>_row_stride elements and holds `inner` contiguous elements, so a
+ *   [T+1, B, C*A] buffer is read in place for T rows.  teacher_dtype / prev_dtype: RLX_DTYPE_F32, _BF16 or _F16.
+ *
+ * rlx_opd_loss_fwd: one streaming pass + a one-block finalize over n = numel(logprobs) f32 elements (< 2^31):
+ *   v = (-logprobs) * advantages;  loss_mask (u8) element e is loss_mask[e / mask_div] (mask_div 1: full shape, A: one entry
+ *   per row of A, the reference's broadcast of a last dimension of 1), loss_mask_sum likewise with msum_div (int64 when
+ *   msum_i64, else f32; may be NULL when max_episode_steps == 0).
+ *   max_episode_steps == 0: loss = masked_mean(v, m) (the masked sum when no element is selected);
+ *   max_episode_steps  > 0: loss = mean((v / ratio) * m), ratio = (loss_mask_sum * 1.0) / max_episode_steps in f32.
+ *   out[RLX_OPD_OUT_FLOATS] as below; the partial sums are f64 per block in `workspace` (no atomics: repeatable bits).
+ * rlx_opd_loss_bwd: d_logprobs[e] = -(((grad_out[0] / out[RLX_OPD_GRAD_DIV]) * m [/ ratio]) * advantages[e]) (grad_out NULL
+ *   = 1), the arguments as in the forward whose `out` it reads. */
+enum rlx_opd_out {
+    RLX_OPD_LOSS = 0,
+    RLX_OPD_POLICY_LOSS = 1,   /* actor/policy_loss */
+    RLX_OPD_REWARD = 2,        /* actor/opd_reward     = masked_mean(adv, m) */
+    RLX_OPD_REVERSE_KL = 3,    /* actor/opd_reverse_kl = masked_mean(-adv, m) */
+    RLX_OPD_GRAD_DIV = 4,      /* the loss's divisor: sum(m) (1 when it is 0) or numel in the ratio form */
+    RLX_OPD_MASK_COUNT = 5,    /* sum(m) */
+    RLX_OPD_OUT_FLOATS = 8
+};
+int rlx_opd_advantages(const void* teacher, int teacher_dtype, int64_t teacher_row_stride, const void* prev, int prev_dtype,
+                       int64_t prev_row_stride, int64_t rows, int64_t inner, float* out, rlx_stream_t stream);
+size_t rlx_opd_loss_workspace_bytes(int64_t n);
+int rlx_opd_loss_fwd(const float* logprobs, const float* advantages, const uint8_t* loss_mask, int mask_div,
+                     const void* loss_mask_sum, int msum_div, int msum_i64, int64_t n, int max_episode_steps, float* out,
+                     void* workspace, size_t workspace_bytes, rlx_stream_t stream);
+int rlx_opd_loss_bwd(const float* advantages, const uint8_t* loss_mask, int mask_div, const void* loss_mask_sum, int msum_div,
+                     int msum_i64, int64_t n, int max_episode_steps, const float* out, const float* grad_out,
+                     float* d_logprobs, rlx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,9 @@ TOK_OUT_FLOATS = 16
 TOK_OUT_NAMES = {"loss": 0, "actor/policy_loss": 1, "actor/policy_loss_abs": 2, "actor/ratio": 3, "actor/ratio_abs": 4,
                  "actor/clipped_ratio": 5, "actor/dual_cliped_ratio": 6, "actor/approx_kl": 7, "actor/clip_fraction": 8,
                  "actor/entropy_loss": 9, "actor/kl_loss": 10, "actor/token_num": 11, "policy_on": 12}
+OPD_OUT_FLOATS = 8  # include/rlx.h: rlx_opd_out
+OPD_OUT_NAMES = {"loss": 0, "actor/policy_loss": 1, "actor/opd_reward": 2, "actor/opd_reverse_kl": 3, "grad_div": 4,
+                 "mask_count": 5}
 
 # name -> (restype, argtypes); kept in one table so tests can check it against include/rlx.h
 PROTOTYPES = {
@@ -244,6 +247,12 @@ PROTOTYPES = {
     "rlx_rollout_metrics_workspace_bytes": (c_size_t, []),
     "rlx_rollout_metrics": (c_int, [POINTER(c_void_p), POINTER(c_int64), c_int, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    "rlx_opd_advantages": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "rlx_opd_loss_workspace_bytes": (c_size_t, [c_int64]),
+    "rlx_opd_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    "rlx_opd_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
     "rlx_xgmi_create": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_void_p), c_void_p]),
     "rlx_xgmi_connect": (c_int, [c_void_p, c_void_p]),
     "rlx_xgmi_connect_local": (c_int, [POINTER(c_void_p), c_int]),
@@ -282,7 +291,7 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 112:
+    if lib.rlx_version() < 113:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents

@@ -1,5 +1,5 @@
-"""Built-in advantage estimators behind the registry names "gae" and "grpo"
-(mirror of rlinf/algorithms/advantages.py:24-121), served by gae_scan.hip / grpo_adv.hip.
+"""Built-in advantage estimators behind the registry names "gae", "grpo", "reinpp" and "opd"
+(mirror of rlinf/algorithms/advantages.py:24-121,300-407), served by gae_scan.hip / grpo_adv.hip / reinpp_adv.hip / opd.hip.
 
 Two entry shapes exist for each name:
   * the reference's callee contract -- flattened ``[T, B]`` tensors, ``fn(**kwargs) -> (advantages,
@@ -142,6 +142,36 @@ def compute_reinpp_advantages(rewards: torch.Tensor, loss_mask: torch.Tensor, gr
                                       use_reinpp_baseline=use_reinpp_baseline, kl_beta=kl_beta, logprob=t(logprob),
                                       ref_logprob=t(ref_logprob), kl_penalty_type=kl_penalty_type)
     return adv.transpose(0, 1), None
+
+
+@register_advantage("opd")
+def compute_opd_advantages(prev_logprobs: torch.Tensor, teacher_logprobs: torch.Tensor,
+                           loss_mask: Optional[torch.Tensor] = None, normalize_advantages: bool = False, **kwargs):
+    """On-policy distillation (advantages.py:367-407): teacher - prev in f32, [T or T+1, B, C*A] -> [T, B, C, A] (trimmed to
+    loss_mask's time length when a mask is given), (advantages, None).  The reference's checks run on the host first, with its
+    messages; then ONE launch of opd.hip reads the kept time rows in place.  The dispatcher hands this function the raw kwargs
+    (registry.py:106-111), so it is its own fast path."""
+    assert teacher_logprobs is not None, "OPD advantage computation requires post-rollout teacher_logprobs."
+    assert prev_logprobs is not None, "OPD advantage computation requires prev_logprobs from student rollout."
+    assert teacher_logprobs.shape == prev_logprobs.shape, (
+        f"teacher_logprobs shape {teacher_logprobs.shape} must match prev_logprobs shape {prev_logprobs.shape}.")
+    assert not normalize_advantages, "VLA-OPD uses raw reverse-KL rewards; set normalize_advantages to False."
+    num_action_chunks = kwargs.get("num_action_chunks", None)
+    assert num_action_chunks is not None, "OPD advantage computation requires num_action_chunks."
+    assert teacher_logprobs.shape[-1] % num_action_chunks == 0, (
+        f"OPD token count {teacher_logprobs.shape[-1]} must be divisible by num_action_chunks {num_action_chunks}.")
+    rows = None
+    if loss_mask is not None:
+        target_steps = loss_mask.shape[0]
+        # dim 0 after the [..., C, A] reshape: the chunk axis itself for a 1-D input
+        first = teacher_logprobs.shape[0] if teacher_logprobs.dim() > 1 else num_action_chunks
+        assert first in {target_steps, target_steps + 1}, (
+            f"OPD advantages time dimension {first} must match loss_mask time dimension {target_steps} or include one "
+            "bootstrap step.")
+        rows = target_steps
+    dev = _u.compute_device(prev_logprobs, teacher_logprobs, loss_mask)
+    adv = ops.opd_advantages(_u.stage(teacher_logprobs, dev), _u.stage(prev_logprobs, dev), int(num_action_chunks), rows)
+    return _u.unstage(adv, prev_logprobs), None
 
 
 _mark_native_adv("gae", _native_gae)

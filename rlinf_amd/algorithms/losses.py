@@ -1,5 +1,6 @@
-"""Built-in policy losses behind the registry names "actor_critic" and "actor"
-(mirror of rlinf/algorithms/losses.py:170-380,397-425,513-535), served by ppo_loss.hip.
+"""Built-in policy losses behind the registry names "actor_critic", "actor", "decoupled_actor_critic" and "opd"
+(mirror of rlinf/algorithms/losses.py:27-167,170-380,383-535), served by ppo_loss.hip / decoupled_loss.hip / token_ops.hip /
+opd.hip.
 
 ``policy_loss(**kwargs)`` in the reference runs preprocess_loss_inputs, the loss, and then ``.item()``
 on every metric (15 device syncs per micro-batch).  Here the embodied entry takes the RAW kwargs the
@@ -16,7 +17,7 @@ from typing import Optional
 import torch
 
 from .. import ops, token_ops
-from .._lib import DPPO_OUT_NAMES, PPO_OUT_NAMES, TOK_OUT_NAMES
+from .._lib import DPPO_OUT_NAMES, OPD_OUT_NAMES, PPO_OUT_NAMES, TOK_OUT_NAMES
 from . import utils as _u
 from .registry import _mark_native_loss, register_policy_loss
 
@@ -271,9 +272,61 @@ def compute_grpo_actor_loss_fn(**kwargs) -> tuple[torch.Tensor, Mapping]:
     return _fused(kwargs, has_critic=False)
 
 
+# ---- on-policy distillation (losses.py:427-505) -------------------------------------------------------------
+_OPD_KEYS = ("actor/policy_loss", "actor/opd_reward", "actor/opd_reverse_kl")
+
+
+def _opd_form(t: torch.Tensor, logprobs: torch.Tensor, name: str) -> torch.Tensor:
+    """The reference's shape rules for loss_mask / loss_mask_sum: one fewer dimension is unsqueezed, a last dimension of 1 is
+    broadcast (the kernel indexes it per row instead of expanding it), anything else is refused with its message."""
+    if t.dim() == logprobs.dim() - 1:
+        t = t.unsqueeze(-1)
+    if t.shape != logprobs.shape:
+        assert t.dim() == logprobs.dim(), f"OPD {name} rank {t.dim()} must match logprobs rank {logprobs.dim()}."
+        assert t.shape[:-1] == logprobs.shape[:-1], (
+            f"OPD {name} shape {t.shape} must match logprobs shape {logprobs.shape} except the token dimension.")
+        assert t.shape[-1] == 1, (
+            f"OPD {name} token dimension {t.shape[-1]} must be 1 or match logprobs token dimension {logprobs.shape[-1]}.")
+    return t
+
+
+@register_policy_loss("opd")
+def compute_opd_actor_loss(logprobs: torch.Tensor, advantages: torch.Tensor, loss_mask: Optional[torch.Tensor] = None,
+                           loss_agg_func=None, max_episode_steps: Optional[int] = None,
+                           loss_mask_sum: Optional[torch.Tensor] = None, **kwargs):
+    """VLA-OPD actor loss agg(-logprobs * stopgrad(advantages), loss_mask) with the reference's signature and asserts
+    (losses.py:427-505), on the tensors preprocess_loss_inputs has shaped ([bsz, C, A] with token-level log-probs).  agg is
+    masked_mean, or masked_mean_ratio with ratio = loss_mask_sum / max_episode_steps when max_episode_steps is given.  Loss and
+    the three metrics come from ONE forward launch pair of opd.hip; metrics are read lazily (one D2H copy)."""
+    assert logprobs.dtype == torch.float32, "logprobs must be float32 to keep numerical stability"
+    assert advantages.dtype == torch.float32, "advantages must be float32 to keep numerical stability"
+    assert advantages.shape == logprobs.shape, (
+        f"OPD advantages shape {advantages.shape} must match logprobs shape {logprobs.shape}.")
+    assert loss_mask is not None, "OPD actor loss requires loss_mask."
+    assert loss_mask_sum is not None, "OPD actor loss requires loss_mask_sum."
+    loss_mask = _opd_form(loss_mask, logprobs, "loss_mask")
+    loss_mask_sum = _opd_form(loss_mask_sum, logprobs, "loss_mask_sum")
+    if max_episode_steps is None and loss_agg_func is not None and getattr(loss_agg_func, "__name__", None) != "masked_mean":
+        raise NotImplementedError("policy_loss(loss_type='opd'): only the masked_mean aggregation (or masked_mean_ratio through "
+                                  "max_episode_steps) is served by the OPD kernel")
+    dev = _u.compute_device(logprobs, advantages, loss_mask, loss_mask_sum)
+    st = lambda t: _u.stage(t, dev)  # noqa: E731
+    loss, out = ops.opd_loss(st(logprobs), st(advantages), st(loss_mask), action_dim=logprobs.shape[-1] if logprobs.dim() else 1,
+                             loss_mask_sum=st(loss_mask_sum), max_episode_steps=max_episode_steps)
+    return loss, LossMetrics(out, False, actor_keys=_OPD_KEYS, names=OPD_OUT_NAMES)
+
+
+def _native_opd_loss(**kwargs):
+    """policy_loss(task_type='embodied', loss_type='opd') on the learner's RAW kwargs ([bsz, C*A] log-probs, [bsz, C, A]
+    advantages, [bsz, C] mask / mask_sum): preprocess_loss_inputs only reshapes and unsqueezes here (views, no copies), and the
+    metrics stay on the device instead of being .item()-ed one by one."""
+    return compute_opd_actor_loss(**_u.preprocess_loss_inputs(**kwargs))
+
+
 _mark_native_loss("actor_critic", compute_ppo_actor_critic_loss)
 _mark_native_loss("actor", compute_grpo_actor_loss_fn)
 _mark_native_loss("decoupled_actor_critic", compute_decoupled_ppo_actor_critic_loss)
+_mark_native_loss("opd", _native_opd_loss)
 
 
 def explained_variance_from_stats(stats: Mapping) -> float:

@@ -164,7 +164,11 @@ def preprocess_loss_inputs(logprobs, old_logprobs, advantages, logprob_type=None
     if logprob_type == "token_level":
         logprobs = logprobs.reshape(bsz, -1, single_action_dim)
         old_logprobs = old_logprobs.reshape(bsz, -1, single_action_dim)
-        advantages = advantages.unsqueeze(-1)
+        if kwargs.get("loss_type") == "opd":  # OPD advantages are per token already (utils.py:318-323)
+            assert advantages.shape == logprobs.shape, (
+                f"OPD advantages shape {advantages.shape} must match logprobs shape {logprobs.shape}.")
+        else:
+            advantages = advantages.unsqueeze(-1)
         loss_mask = None if loss_mask is None else loss_mask.unsqueeze(-1)
         loss_mask_sum = None if loss_mask_sum is None else loss_mask_sum.unsqueeze(-1)
     elif logprob_type == "action_level":

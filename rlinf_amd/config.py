@@ -232,6 +232,11 @@ def validate_embodied_cfg(cfg):
     assert model_cfg.model_type in SUPPORTED_EMBODIED_MODELS, (
         f"Model type: '{model_cfg.model_type}' is not supported by the embodied runner. "
         f"Supported embodied models: {sorted(SUPPORTED_EMBODIED_MODELS)}.")
+    if cfg.algorithm.get("adv_type") == "opd":
+        # the teacher pass in front of the OPD advantages runs for OpenVLA models only (embodied_fsdp_actor_worker.py:337-340);
+        # this build's learner serves mlp_policy, so the run fails here, with the reference's message, instead of at advantage time
+        assert model_cfg.model_type in ("openvla", "openvla_oft"), (
+            "OPD teacher logprob computation currently supports OpenVLA models.")
     cfg.runner.val_check_interval = cfg.runner.get("val_check_interval", -1)
     cfg.env.train.rollout_epoch = cfg.env.train.get("rollout_epoch", 1)
     if cfg.algorithm.loss_type in ("actor_critic", "decoupled_actor_critic"):

@@ -10,7 +10,8 @@ registry (rlinf/models/__init__.py:31-53, ``force=True``), so the unmodified lea
 
 Because RLinf's ``policy_loss`` runs preprocess_loss_inputs BEFORE the registered callee and ``.item()``s
 every metric after it, the callees registered here take the already-shaped tensors (sub_per_adv == raw
-== 1 per element) and return plain tensors, exactly what that caller expects.
+== 1 per element) and return plain tensors, exactly what that caller expects.  The on-policy distillation names ("opd", advantage
+and loss) are replaced only in an RLinf that registers them itself, i.e. one whose dispatcher has the OPD arm.
 """
 
 from __future__ import annotations
@@ -21,15 +22,21 @@ def register() -> None:
     from rlinf.algorithms import registry as ref_registry  # the REAL package; ImportError is logged by RLinf
 
     from rlinf_amd import ops
-    from rlinf_amd._lib import DPPO_OUT_NAMES, PPO_OUT_NAMES, TOK_OUT_NAMES
+    from rlinf_amd._lib import DPPO_OUT_NAMES, OPD_OUT_NAMES, PPO_OUT_NAMES, TOK_OUT_NAMES
     from rlinf_amd.algorithms import advantages as adv
     from rlinf_amd.algorithms import utils as u
-    from rlinf_amd.algorithms.losses import (_ACTOR_KEYS, _CRITIC_KEYS, _DECOUPLED_KEYS, _EV_MAP, _TOKEN_KEYS_ZERO,
-                                             _token_fused)
+    from rlinf_amd.algorithms.losses import (_ACTOR_KEYS, _CRITIC_KEYS, _DECOUPLED_KEYS, _EV_MAP, _OPD_KEYS, _TOKEN_KEYS_ZERO,
+                                             _token_fused, compute_opd_actor_loss)
 
     ref_registry.register_advantage("gae")(adv.compute_gae_advantages_and_returns)
     ref_registry.register_advantage("grpo")(adv.compute_grpo_advantages)
     ref_registry.register_advantage("reinpp")(adv.compute_reinpp_advantages)  # reasoning: [1, B] rewards, [L, B] tensors
+    # "opd" only where this RLinf registers it itself: its dispatcher then has the OPD arm that hands the callee the raw kwargs
+    # (registry.py:106-111); an RLinf without that arm would route the name through its [T, B] pre-processing instead
+    opd_adv = "opd" in getattr(ref_registry, "ADV_REGISTRY", {})
+    opd_loss = "opd" in getattr(ref_registry, "LOSS_REGISTRY", {})
+    if opd_adv:
+        ref_registry.register_advantage("opd")(adv.compute_opd_advantages)
 
     def _reasoning_actor(kw):
         """task_type='reasoning': [bsz, seq] token tensors and the learner's loss_agg_func (fsdp_actor_worker.py:736-750)."""
@@ -96,6 +103,13 @@ def register() -> None:
             metrics["actor/current_version"] = out.new_tensor(float(cur))
         return loss, metrics
 
+    def _shaped_opd(**kw):
+        """opd on the [bsz, C, A] tensors preprocess_loss_inputs has shaped (losses.py:427-505); the metrics go back as 0-dim
+        device tensors for the caller's .item()."""
+        loss, m = compute_opd_actor_loss(**kw)
+        out = m.device_vector
+        return loss, {k: out[OPD_OUT_NAMES[k]] for k in _OPD_KEYS}
+
     # the model leg (rlinf/models/__init__.py:31-53): cfg.actor.model.model_type == "mlp_policy" now builds the HIP module in
     # the learner (embodied_fsdp_actor_worker.py:117-127) and in the rollout worker (huggingface_worker.py:137-151)
     from rlinf import models as ref_models
@@ -107,5 +121,7 @@ def register() -> None:
     ref_registry.register_policy_loss("actor_critic")(_shaped_loss(True))
     ref_registry.register_policy_loss("actor")(_shaped_loss(False))
     ref_registry.register_policy_loss("decoupled_actor_critic")(_shaped_decoupled)
+    if opd_loss:
+        ref_registry.register_policy_loss("opd")(_shaped_opd)
     if not torch.cuda.is_available():
         raise RuntimeError("rlinf_amd.ext registered HIP kernels but no HIP device is visible")

@@ -558,6 +558,129 @@ def ppo_loss_bwd_raw(params: PpoLossParams, n_adv: int, g_logp, g_value, out, gr
 
 
 # --------------------------------------------------------------------------------------------
+# a19c  on-policy distillation (OPD): advantage and loss
+# --------------------------------------------------------------------------------------------
+_OPD_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def _opd_rows(t: torch.Tensor, num_action_chunks: int) -> torch.Tensor:
+    """[T, ..., C*A] -> a [T, ..., C, A] view whose rows (dim 0) hold contiguous elements; only a tensor whose rows are not
+    contiguous is copied.  Dtypes other than f32 / bf16 / f16 are converted to f32 first, as ``.float()`` would."""
+    if t.dtype not in _OPD_DTYPES:
+        t = t.float()
+    v = t.reshape(*t.shape[:-1], num_action_chunks, -1)
+    if v.shape[0] > 0 and not v[0].is_contiguous():
+        v = v.contiguous()
+    return v
+
+
+def opd_advantages(teacher_logprobs: torch.Tensor, prev_logprobs: torch.Tensor, num_action_chunks: int,
+                   rows: Optional[int] = None) -> torch.Tensor:
+    """(teacher.float() - prev.float()) reshaped to [..., C, A], first ``rows`` entries of dim 0 (all when None): ONE launch of
+    rlx_opd_advantages, f32 out.  The caller has checked shapes (algorithms/advantages.py holds the reference's asserts)."""
+    lib = _lib.load()
+    dev = _dev(teacher_logprobs, prev_logprobs)
+    t = _opd_rows(teacher_logprobs, int(num_action_chunks))
+    p = _opd_rows(prev_logprobs, int(num_action_chunks))
+    if t.shape != p.shape:
+        raise RlxError(f"teacher_logprobs {tuple(teacher_logprobs.shape)} and prev_logprobs {tuple(prev_logprobs.shape)} differ")
+    n_rows = t.shape[0] if rows is None else int(rows)
+    if not 0 <= n_rows <= t.shape[0]:
+        raise RlxError(f"rows={n_rows} outside [0, {t.shape[0]}]")
+    out = torch.empty((n_rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+    inner = out[0].numel() if n_rows > 0 else 0
+    with torch.cuda.device(dev):
+        _lib.check(lib.rlx_opd_advantages(t.data_ptr(), _OPD_DTYPES[t.dtype], t.stride(0) if t.dim() else 1, p.data_ptr(),
+                                          _OPD_DTYPES[p.dtype], p.stride(0) if p.dim() else 1, n_rows, inner, out.data_ptr(),
+                                          _stream_ptr(dev)), "rlx_opd_advantages")
+    return out
+
+
+def _opd_div(t: Optional[torch.Tensor], n: int, action_dim: int, name: str) -> int:
+    """1 when ``t`` holds one entry per loss element, ``action_dim`` when it holds one per row of action_dim elements."""
+    if t is None:
+        return 1
+    if t.numel() == n:
+        return 1
+    if action_dim >= 1 and t.numel() * action_dim == n:
+        return action_dim
+    raise RlxError(f"{name} has {t.numel()} elements; expected {n} or {n // max(action_dim, 1)}")
+
+
+class _OpdLossFn(torch.autograd.Function):
+    """rlx_opd_loss_fwd / rlx_opd_loss_bwd.  The advantages are a stop-gradient input (``advantages.detach()``)."""
+
+    @staticmethod
+    def forward(ctx, logprobs, advantages, loss_mask, mask_div, loss_mask_sum, msum_div, max_episode_steps: int):
+        lib = _lib.load()
+        dev = logprobs.device
+        lp = logprobs.contiguous()
+        n = lp.numel()
+        i64 = int(loss_mask_sum is not None and loss_mask_sum.dtype == torch.int64)
+        out = torch.empty((_lib.OPD_OUT_FLOATS,), dtype=torch.float32, device=dev)
+        ws_bytes = lib.rlx_opd_loss_workspace_bytes(n)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rlx_opd_loss_fwd(lp.data_ptr(), advantages.data_ptr(), loss_mask.data_ptr(), mask_div,
+                                            _ptr(loss_mask_sum), msum_div, i64, n, max_episode_steps, out.data_ptr(),
+                                            ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_opd_loss_fwd")
+        ctx.save_for_backward(advantages, loss_mask, loss_mask_sum if loss_mask_sum is not None else out, out)
+        ctx.geom = (mask_div, msum_div, i64, n, max_episode_steps, loss_mask_sum is not None)
+        ctx.lp_shape = logprobs.shape
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_out):
+        lib = _lib.load()
+        adv, mask, msum, out = ctx.saved_tensors
+        mask_div, msum_div, i64, n, mes, has_msum = ctx.geom
+        dev = adv.device
+        go = grad_loss.to(dtype=torch.float32).contiguous()
+        d_lp = torch.empty((n,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rlx_opd_loss_bwd(adv.data_ptr(), mask.data_ptr(), mask_div, msum.data_ptr() if has_msum else None,
+                                            msum_div, i64, n, mes, out.data_ptr(), go.data_ptr(), d_lp.data_ptr(),
+                                            _stream_ptr(dev)), "rlx_opd_loss_bwd")
+        return d_lp.view(ctx.lp_shape), None, None, None, None, None, None
+
+
+def opd_loss(logprobs: torch.Tensor, advantages: torch.Tensor, loss_mask: torch.Tensor, *, action_dim: int,
+             loss_mask_sum: Optional[torch.Tensor] = None, max_episode_steps: Optional[int] = None):
+    """OPD actor loss agg(-logprobs * advantages.detach(), loss_mask) and its metrics in ONE forward launch pair (stream pass +
+    finalize) and ONE backward launch.  ``logprobs`` f32 with a last dimension of ``action_dim`` elements per row (any leading
+    shape); ``advantages`` f32 of the same element count; ``loss_mask`` / ``loss_mask_sum`` with one entry per element or one
+    per row (the reference's broadcast of a last dimension of 1).  ``max_episode_steps`` selects masked_mean_ratio with
+    ratio = loss_mask_sum / max_episode_steps, else masked_mean.  Returns (loss 0-dim with grad, out f32[8] on device, see
+    _lib.OPD_OUT_NAMES)."""
+    dev = _dev(logprobs, advantages, loss_mask, loss_mask_sum)
+    for name, t in (("logprobs", logprobs), ("advantages", advantages)):
+        if t.dtype != torch.float32:
+            raise RlxError(f"{name} must be float32 to keep numerical stability")
+    n = logprobs.numel()
+    if advantages.numel() != n:
+        raise RlxError(f"advantages has {advantages.numel()} elements, expected {n}")
+    if loss_mask is None:
+        raise RlxError("opd_loss needs loss_mask")
+    mes = 0
+    if max_episode_steps is not None:
+        if int(max_episode_steps) != max_episode_steps or int(max_episode_steps) <= 0:
+            raise RlxError(f"max_episode_steps must be a positive integer, got {max_episode_steps!r}")
+        if loss_mask_sum is None:
+            raise RlxError("max_episode_steps needs loss_mask_sum")
+        mes = int(max_episode_steps)
+    m8 = _as_u8(loss_mask)
+    mdiv = _opd_div(m8, n, int(action_dim), "loss_mask")
+    msum, sdiv = None, 1
+    if loss_mask_sum is not None and mes > 0:
+        msum = loss_mask_sum if loss_mask_sum.dtype in (torch.int64, torch.float32) else loss_mask_sum.float()
+        msum = msum.contiguous()
+        sdiv = _opd_div(msum, n, int(action_dim), "loss_mask_sum")
+    with torch.cuda.device(dev):
+        return _OpdLossFn.apply(logprobs, advantages.detach().contiguous(), m8, mdiv, msum, sdiv, mes)
+
+
+# --------------------------------------------------------------------------------------------
 # a16  shuffle gather
 # --------------------------------------------------------------------------------------------
 def gather_rows(fields: list, index: torch.Tensor, outs: Optional[list] = None) -> list:
