@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 113 /* 0.1.3: bumped whenever an argument struct or a signature changes (0.1.3: the OPD entries rlx_opd_*; round 6: rlx_xgmi_self_timing, the
+#define RLX_VERSION 114 /* 0.1.4: bumped whenever an argument struct or a signature changes (0.1.4: rlx_grpo_dynamic_adv,
+                           * rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries rlx_opd_*; round 6: rlx_xgmi_self_timing, the
                            * exchange inside rlx_xgmi_clip_adamw_step under sync_words; round 5: rlx_categorical_sample's
                            * softmax_lanes, rlx_adamw_params.sync_words; round 4's struct growth had left it at 100) */
 
@@ -698,6 +699,41 @@ size_t rlx_reinpp_workspace_bytes(int64_t bsz);
 int rlx_reinpp_seq_adv(const float* rewards, const uint8_t* loss_mask, const float* logprob, const float* ref_logprob,
                        int kl_type, float kl_beta, float* advantages, int64_t bsz, int64_t seq, void* workspace,
                        size_t workspace_bytes, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * t3c  grpo_dynamic_adv  <- adv_type "grpo_dynamic" on reasoning batches: preprocess_reasoning_advantages_inputs
+ *                           rlinf/algorithms/utils.py:207-215 + compute_grpo_dynamic_advantages rlinf/algorithms/advantages.py:167-299
+ *                           + postprocess_reasoning_advantages_outputs rlinf/algorithms/utils.py:265-277
+ *   rewards [num_seq] (rewards_dtype RLX_DTYPE_F32 or _BF16), loss_mask [num_seq, seq] u8 -> advantages [num_seq, seq] in the
+ *   rewards' dtype = adv(row) * mask (a multiplication: NaN stays NaN, a negative advantage gives -0.0 where masked).
+ *   plan (int32, device): traj_of_row[num_seq] (idx_to_traj) | order[num_seq] (rows sorted stably by trajectory) |
+ *   traj_offsets[num_traj + 1]; every id < num_traj and num_traj % group_size == 0 (the host builds and checks it).
+ *   mode RLX_GRPO_DYN_TURN: mean / unbiased std over all turns of the row's question (trajectory / group_size);
+ *   RLX_GRPO_DYN_TRAJECTORY: over the question's group_size trajectory rewards, each the mean of its turns (0 when it has none).
+ *   adv = (r - mean) / (std + eps), std NaN for a single value.  One launch; sums in f64 in a fixed order, so repeated launches
+ *   give the same bits.  Loss mask 4-byte aligned, advantages 16-byte (f32) / 8-byte (bf16) aligned.
+ * ------------------------------------------------------------------------------------------ */
+enum rlx_grpo_dyn_mode { RLX_GRPO_DYN_TRAJECTORY = 0, RLX_GRPO_DYN_TURN = 1 };
+int rlx_grpo_dynamic_adv(const void* rewards, int rewards_dtype, const int32_t* plan, const uint8_t* loss_mask,
+                         void* advantages, int64_t num_seq, int64_t num_traj, int64_t seq, int group_size, int mode,
+                         float eps, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * t3d  loss scales  <- group_scale / agent_scale / turn_scale rlinf/algorithms/loss_scales.py (registry names "group_level",
+ *                      "agent_level", "turn_level"; LOSS_SCALE_REGISTRY rlinf/algorithms/registry.py:128-147), in place
+ * rlx_loss_scale_rows: x[row, :] *= row_factor[row] (row_factor NULL: *= factor), x [rows, cols] f32 or bf16 (dtype); one
+ *   f32 multiply per element, as torch's `t *= python_float` (the float rounded to f32 once).  group_level: rows = 1,
+ *   cols = numel, factor = num_seq * dp_world_size / actor_global_batch_size; agent_level: row_factor = f32((1 / A_i) / T_ia).
+ * rlx_loss_scale_turn: one workgroup per (trajectory, sub-trajectory) group; plan (int32, device) = order[num_seq] (rows
+ *   grouped) | group_offsets[num_groups + 1].  Row t of a group of T rows whose mask counts sum to S is scaled by
+ *   f32((T * |o_t|) / S) (f64 division of exact integers, |o_t| = nonzero bytes of response_mask[t]).  A group with S == 0 is
+ *   left as it is and sets *zero_flag = 1 (the caller zeroes it first); the reference raises ZeroDivisionError there.
+ *   response_mask 4-byte aligned, loss_scales 16-byte (f32) / 8-byte (bf16) aligned.
+ * ------------------------------------------------------------------------------------------ */
+int rlx_loss_scale_rows(void* x, int dtype, const float* row_factor, float factor, int64_t rows, int64_t cols,
+                        rlx_stream_t stream);
+int rlx_loss_scale_turn(void* loss_scales, int dtype, const uint8_t* response_mask, const int32_t* plan, int64_t num_seq,
+                        int64_t num_groups, int64_t seq, int32_t* zero_flag, rlx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * t5  gae_seq  <- adv_type "gae" on reasoning batches: preprocess_reasoning_advantages_inputs rlinf/algorithms/utils.py:177-262

@@ -1,5 +1,6 @@
-"""Built-in advantage estimators behind the registry names "gae", "grpo", "reinpp" and "opd"
-(mirror of rlinf/algorithms/advantages.py:24-121,300-407), served by gae_scan.hip / grpo_adv.hip / reinpp_adv.hip / opd.hip.
+"""Built-in advantage estimators behind the registry names "gae", "grpo", "grpo_dynamic", "reinpp" and "opd"
+(mirror of rlinf/algorithms/advantages.py:24-121,167-407), served by gae_scan.hip / grpo_adv.hip / grpo_dynamic.hip /
+reinpp_adv.hip / opd.hip.
 
 Two entry shapes exist for each name:
   * the reference's callee contract -- flattened ``[T, B]`` tensors, ``fn(**kwargs) -> (advantages,
@@ -174,8 +175,65 @@ def compute_opd_advantages(prev_logprobs: torch.Tensor, teacher_logprobs: torch.
     return _u.unstage(adv, prev_logprobs), None
 
 
+def _grpo_dynamic_checks(num_rewards: int, group_size: int, idx_to_traj, advantage_mode: str) -> list:
+    """The reference's host-side checks, in its order and with its messages (advantages.py:209-222,296-299), before any device
+    work.  Returns idx_to_traj as a list of ints."""
+    ids = token_ops.traj_ids(idx_to_traj)
+    num_sequence = len(ids)
+    assert num_rewards == num_sequence, f"Rewards size mismatch: {num_rewards} != {num_sequence}"
+    num_trajectories = max(ids) + 1
+    num_trajectories // group_size  # noqa: B018  (num_questions: a group_size of 0 raises here, as in the reference)
+    assert num_trajectories % group_size == 0, (
+        f"num_trajectories {num_trajectories} not divisible by group_size {group_size}")
+    if advantage_mode not in ("trajectory", "turn"):
+        raise ValueError(f"Invalid advantage_mode: {advantage_mode}. Must be 'trajectory' or 'turn'")
+    return ids
+
+
+def _grpo_dynamic_seq(rewards_flat, mask_rows, group_size, ids, advantage_mode):
+    """[num_seq] rewards, [num_seq, seq] mask -> [num_seq, seq] advantages in the rewards' dtype (f16 / f64 rewards are computed
+    in f32 and cast back)."""
+    dev = _u.compute_device(rewards_flat, mask_rows)
+    r = _u.stage(rewards_flat, dev)
+    kernel_dtype = r.dtype if r.dtype in (torch.float32, torch.bfloat16) else torch.float32
+    plan = token_ops.GrpoDynamicPlan(ids, int(group_size), dev)
+    adv = token_ops.grpo_dynamic_adv(r.to(kernel_dtype), _u.stage(mask_rows, dev), plan, advantage_mode)
+    return adv if adv.dtype == rewards_flat.dtype else adv.to(rewards_flat.dtype)
+
+
+@register_advantage("grpo_dynamic")
+def compute_grpo_dynamic_advantages(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: int, idx_to_traj,
+                                    advantage_mode: str = "turn", **kwargs):
+    """Multi-turn GRPO (advantages.py:167-299), the reference's callee contract: rewards [num_seq, 1], loss_mask [seq_len,
+    num_seq] bool, idx_to_traj turn -> trajectory (a list of ints or a 1-D integer tensor, any order) -> (advantages [seq_len,
+    num_seq], None).  advantage_mode "turn": mean / std over every turn of a question (trajectory // group_size);
+    "trajectory": over the question's group_size trajectory rewards, each the mean of its turns.  One launch of grpo_dynamic.hip
+    on the [num_seq, seq_len] layout; this entry transposes on the way in and out, ``calculate_adv_and_returns`` does not."""
+    rewards_flat = rewards.squeeze(-1)
+    ids = _grpo_dynamic_checks(rewards_flat.numel(), group_size, idx_to_traj, advantage_mode)
+    adv = _grpo_dynamic_seq(rewards_flat.reshape(-1), loss_mask.transpose(0, 1), group_size, ids, advantage_mode)
+    return _u.unstage(adv, loss_mask).transpose(0, 1), None
+
+
+def _native_grpo_dynamic_reasoning(*, rewards, loss_mask, group_size, idx_to_traj, num_sequence=None, advantage_mode="turn",
+                                   **kwargs):
+    """Multi-turn GRPO on the learner's [num_seq, seq_len] tensors (ma_megatron_actor_worker.py:591-610) -> (advantages
+    [num_seq, seq_len] contiguous, None): replaces preprocess_reasoning_advantages_inputs + compute_grpo_dynamic_advantages +
+    postprocess (utils.py:207-215,265-277) without a transpose."""
+    if loss_mask.dim() != 2:
+        return None  # the generic route fails the way the reference does
+    if rewards.ndim != 1:
+        raise AssertionError(f"Unsupported reward shape {rewards.shape}")
+    if num_sequence is None or rewards.numel() != num_sequence:
+        return None  # the reference's reshape(-1, num_sequence) decides what happens
+    ids = _grpo_dynamic_checks(rewards.numel(), group_size, idx_to_traj, advantage_mode)
+    adv = _grpo_dynamic_seq(rewards, loss_mask, group_size, ids, advantage_mode)
+    return _u.unstage(adv, loss_mask), None
+
+
 _mark_native_adv("gae", _native_gae)
 _mark_native_adv("grpo", _native_grpo)
 _mark_native_adv("gae", _native_gae_reasoning, task_type="reasoning")
 _mark_native_adv("grpo", _native_grpo_reasoning, task_type="reasoning")
 _mark_native_adv("reinpp", _native_reinpp_reasoning, task_type="reasoning")
+_mark_native_adv("grpo_dynamic", _native_grpo_dynamic_reasoning, task_type="reasoning")

@@ -1,4 +1,4 @@
-"""Plugin boundary: same names, argument meaning and error behaviour as rlinf/algorithms/registry.py:30-124.
+"""Plugin boundary: same names, argument meaning and error behaviour as rlinf/algorithms/registry.py:30-147.
 
 ``register_advantage`` / ``register_policy_loss`` keep the reference's "last registration wins,
 names are lower-cased" rule, ``get_*`` raise ValueError for unknown names, and the two unified
@@ -119,3 +119,26 @@ def calculate_adv_and_returns(**kwargs):
     kwargs = _u.preprocess_reasoning_advantages_inputs(**kwargs)
     advantages, returns = fn(**kwargs)
     return _u.postprocess_reasoning_advantages_outputs(advantages, returns)
+
+
+LOSS_SCALE_REGISTRY: dict[str, Callable] = {}
+
+
+def register_loss_scale(name: str):
+    """Decorator storing a loss-scale process ``fn(context, batch) -> batch`` under ``name.lower()`` (registry.py:128-135)."""
+
+    def decorator(fn):
+        LOSS_SCALE_REGISTRY[name.lower()] = fn
+        return fn
+
+    return decorator
+
+
+def get_loss_scales(names: list[str]) -> list[Callable]:
+    """The registered processes for ``names``, in order; lookup is case-sensitive, as in the reference (registry.py:138-144)."""
+    loss_scales = []
+    for name in names:
+        if name not in LOSS_SCALE_REGISTRY:
+            raise ValueError(f"Loss scale process {name} not registered")
+        loss_scales.append(LOSS_SCALE_REGISTRY[name])
+    return loss_scales

@@ -11,7 +11,8 @@ registry (rlinf/models/__init__.py:31-53, ``force=True``), so the unmodified lea
 Because RLinf's ``policy_loss`` runs preprocess_loss_inputs BEFORE the registered callee and ``.item()``s
 every metric after it, the callees registered here take the already-shaped tensors (sub_per_adv == raw
 == 1 per element) and return plain tensors, exactly what that caller expects.  The on-policy distillation names ("opd", advantage
-and loss) are replaced only in an RLinf that registers them itself, i.e. one whose dispatcher has the OPD arm.
+and loss) are replaced only in an RLinf that registers them itself, i.e. one whose dispatcher has the OPD arm.  "grpo_dynamic" is
+likewise replaced only where RLinf registers it; the loss scales ("group_level", "agent_level", "turn_level") only in an RLinf that has register_loss_scale.
 """
 
 from __future__ import annotations
@@ -37,6 +38,17 @@ def register() -> None:
     opd_loss = "opd" in getattr(ref_registry, "LOSS_REGISTRY", {})
     if opd_adv:
         ref_registry.register_advantage("opd")(adv.compute_opd_advantages)
+    # multi-turn GRPO ([num_seq, 1] rewards, [seq_len, num_seq] mask, idx_to_traj) only where this RLinf registers it itself: its
+    # reasoning pre-processing then has the grpo_dynamic arm (utils.py:207-215) that shapes the callee's inputs
+    if "grpo_dynamic" in getattr(ref_registry, "ADV_REGISTRY", {}):
+        ref_registry.register_advantage("grpo_dynamic")(adv.compute_grpo_dynamic_advantages)
+    # the loss-scale processes only where this RLinf has their registry (registry.py:128-147)
+    if hasattr(ref_registry, "register_loss_scale"):
+        from rlinf_amd.algorithms import loss_scales as ls
+
+        ref_registry.register_loss_scale("group_level")(ls.group_scale)
+        ref_registry.register_loss_scale("agent_level")(ls.agent_scale)
+        ref_registry.register_loss_scale("turn_level")(ls.turn_scale)
 
     def _reasoning_actor(kw):
         """task_type='reasoning': [bsz, seq] token tensors and the learner's loss_agg_func (fsdp_actor_worker.py:736-750)."""

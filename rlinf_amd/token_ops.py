@@ -1,5 +1,6 @@
-"""Tensor-level launchers of the token tier (include/rlx.h t1-t3): per-token log-prob / entropy over
-vocabulary logits, the reasoning learner's micro-batch loss, GRPO advantages in the [bsz, seq] layout.
+"""Tensor-level launchers of the token tier (include/rlx.h t1-t5): per-token log-prob / entropy over
+vocabulary logits, the reasoning learner's micro-batch loss, GRPO / multi-turn GRPO advantages in the [bsz, seq] layout and
+the dynamic-batch loss scales.
 
 Same rules as ``ops.py``: HIP tensors only, no eager path; torch supplies memory, the stream and autograd
 plumbing.
@@ -423,3 +424,176 @@ def gae_seq(values: torch.Tensor, rewards: torch.Tensor, gamma: float = 1.0, gae
         _lib.check(lib.rlx_gae_seq(v.data_ptr(), r.data_ptr(), adv.data_ptr(), ret.data_ptr(), bsz, seq, float(gamma),
                                    float(gamma * gae_lambda), ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "rlx_gae_seq")
     return adv, ret
+
+
+# ---- multi-turn GRPO (grpo_dynamic) and the dynamic-batch loss scales (include/rlx.h t3c / t3d) ------------------------------
+def traj_ids(idx_to_traj) -> list:
+    """idx_to_traj as the reference iterates it: a list of Python ints (a 1-D integer tensor is accepted too)."""
+    if isinstance(idx_to_traj, torch.Tensor):
+        if idx_to_traj.dim() != 1 or idx_to_traj.is_floating_point() or idx_to_traj.is_complex():
+            raise RlxError(f"idx_to_traj must be a 1-D integer tensor or a list of ints (got {idx_to_traj.dtype}, "
+                           f"shape {tuple(idx_to_traj.shape)})")
+        return idx_to_traj.tolist()
+    return list(idx_to_traj)
+
+
+def grpo_dynamic_csr(idx_to_traj, num_traj: Optional[int] = None):
+    """Host CSR of idx_to_traj: (order, traj_offsets) as int64 numpy arrays -- the turn rows sorted stably by trajectory (turn
+    order kept inside a trajectory) and offsets[num_traj + 1].  Trajectories with no turns get an empty range."""
+    import numpy as np
+
+    ids = np.asarray(traj_ids(idx_to_traj), dtype=np.int64).reshape(-1)
+    if ids.size and ids.min() < 0:
+        raise RlxError("idx_to_traj holds a negative trajectory id")
+    n_traj = int(ids.max()) + 1 if ids.size else 0
+    if num_traj is not None:
+        if num_traj < n_traj:
+            raise RlxError(f"num_traj {num_traj} < max(idx_to_traj) + 1 = {n_traj}")
+        n_traj = int(num_traj)
+    order = np.argsort(ids, kind="stable")
+    offsets = np.zeros(n_traj + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ids, minlength=n_traj), out=offsets[1:])
+    return order.astype(np.int64), offsets
+
+
+def _to_device_i32(*parts, device) -> torch.Tensor:
+    import numpy as np
+
+    host = torch.from_numpy(np.concatenate([np.asarray(p, dtype=np.int32) for p in parts]))
+    if host.numel() > 0x7fffffff:
+        raise RlxError("plan too large")
+    return host.pin_memory().to(device, non_blocking=True)
+
+
+class GrpoDynamicPlan:
+    """Device plan of rlx_grpo_dynamic_adv: int32 traj_of_row | order | traj_offsets, built on the host in O(num_seq) and copied
+    to the device once.  Build it outside a graph capture; the launch itself is capturable."""
+
+    def __init__(self, idx_to_traj, group_size: int, device):
+        ids = traj_ids(idx_to_traj)
+        order, offsets = grpo_dynamic_csr(ids)
+        self.num_seq, self.num_traj, self.group_size = len(ids), len(offsets) - 1, int(group_size)
+        if self.group_size < 1 or self.num_traj % self.group_size != 0:
+            raise RlxError(f"num_trajectories {self.num_traj} not divisible by group_size {self.group_size}")
+        if self.num_seq >= 2 ** 31:
+            raise RlxError("grpo_dynamic: more than 2^31 - 1 turns")
+        self.plan = _to_device_i32(ids, order, offsets, device=torch.device(device))
+
+
+def grpo_dynamic_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, plan: GrpoDynamicPlan, mode: str = "turn",
+                     eps: float = 1e-6) -> torch.Tensor:
+    """rewards [num_seq] f32 / bf16, loss_mask [num_seq, seq] bool / u8 -> advantages [num_seq, seq] in the rewards' dtype:
+    the turn's multi-turn GRPO advantage times the mask (advantages.py:167-299), ONE launch, no host sync."""
+    dev = _dev(rewards, loss_mask, plan.plan)
+    if mode not in _lib.GRPO_DYN_MODES:
+        raise RlxError(f"grpo_dynamic_adv: mode {mode!r} is not 'trajectory' or 'turn'")
+    if rewards.dtype not in _DTYPES:
+        raise RlxError(f"grpo_dynamic_adv: rewards must be float32 or bfloat16 (got {rewards.dtype})")
+    if loss_mask.dim() != 2 or rewards.numel() != plan.num_seq or loss_mask.shape[0] != plan.num_seq:
+        raise RlxError(f"grpo_dynamic_adv: rewards [num_seq], loss_mask [num_seq, seq] with num_seq = {plan.num_seq} "
+                       f"(got {tuple(rewards.shape)}, {tuple(loss_mask.shape)})")
+    r = rewards.reshape(-1).contiguous()
+    m = _as_u8(loss_mask)
+    if m.data_ptr() % 4:
+        m = m.clone()
+    num_seq, seq = loss_mask.shape
+    adv = torch.empty((num_seq, seq), dtype=rewards.dtype, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rlx_grpo_dynamic_adv(r.data_ptr(), _DTYPES[r.dtype], plan.plan.data_ptr(), m.data_ptr(),
+                                                    adv.data_ptr(), num_seq, plan.num_traj, seq, plan.group_size,
+                                                    _lib.GRPO_DYN_MODES[mode], float(eps), _stream_ptr(dev)),
+                   "rlx_grpo_dynamic_adv")
+    return adv
+
+
+def loss_scale_groups(idx_to_traj, idx_to_sub_traj):
+    """Host grouping of the loss scales (loss_scales.py): turn rows grouped by (trajectory, sub-trajectory).  Returns int64
+    numpy arrays (order, group_offsets, agents) -- rows of a group contiguous in `order` (turn order kept), offsets[num_groups
+    + 1], and per group A_i, the number of distinct sub-trajectories of its trajectory."""
+    import numpy as np
+
+    traj = np.asarray(traj_ids(idx_to_traj), dtype=np.int64).reshape(-1)
+    sub = np.asarray(list(idx_to_sub_traj), dtype=np.int64).reshape(-1)
+    if sub.size != traj.size:
+        raise RlxError(f"idx_to_sub_traj has {sub.size} entries, idx_to_traj {traj.size}")
+    if traj.size == 0:
+        return np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(0, np.int64)
+    order = np.lexsort((sub, traj))  # stable: equal (traj, sub) keys keep their turn order
+    t, s = traj[order], sub[order]
+    new = np.ones(traj.size, dtype=bool)
+    new[1:] = (t[1:] != t[:-1]) | (s[1:] != s[:-1])
+    starts = np.flatnonzero(new)
+    offsets = np.append(starts, traj.size).astype(np.int64)
+    gtraj = t[starts]
+    tstart = np.ones(gtraj.size, dtype=bool)
+    tstart[1:] = gtraj[1:] != gtraj[:-1]
+    run = np.cumsum(tstart) - 1  # trajectory run of each group
+    agents = np.bincount(run)[run]
+    return order.astype(np.int64), offsets, agents.astype(np.int64)
+
+
+def agent_level_factors(order, offsets, agents):
+    """Per-row f32 factor of agent_level: (1 / A_i) / T_ia in f64, as the reference's Python floats, rounded to f32 once."""
+    import numpy as np
+
+    turns = np.diff(offsets)
+    f = (1.0 / agents.astype(np.float64)) / turns.astype(np.float64)
+    out = np.empty(order.size, dtype=np.float32)
+    out[order] = np.repeat(f, turns).astype(np.float32)
+    return out
+
+
+def _scaled_dtype(x: torch.Tensor, who: str) -> int:
+    if x.dtype not in _DTYPES:
+        raise RlxError(f"{who}: float32 or bfloat16 tensor expected (got {x.dtype})")
+    if not x.is_contiguous():
+        raise RlxError(f"{who}: the tensor scaled in place must be contiguous")
+    if x.data_ptr() % (16 if x.dtype == torch.float32 else 8):
+        raise RlxError(f"{who}: the tensor scaled in place is misaligned")
+    return _DTYPES[x.dtype]
+
+
+def scale_rows_(x: torch.Tensor, factor: float = 1.0, row_factors: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x *= factor (row_factors None) or x[row] *= row_factors[row] (f32 [rows]), in place, one launch: the f32 product of each
+    element with the factor rounded to f32 -- torch's `t *= python_float` (loss_scales.py group_scale / agent_scale)."""
+    dev = _dev(x, row_factors)
+    dt = _scaled_dtype(x, "scale_rows_")
+    if row_factors is None:
+        rows, cols = 1, x.numel()
+    else:
+        if x.dim() < 1 or row_factors.dtype != torch.float32 or row_factors.numel() != x.shape[0]:
+            raise RlxError("scale_rows_: row_factors must be f32 [x.shape[0]]")
+        rows, cols = x.shape[0], (x.numel() // x.shape[0] if x.shape[0] else 0)
+        row_factors = row_factors.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rlx_loss_scale_rows(x.data_ptr(), dt, _ptr(row_factors), float(factor), rows, cols,
+                                                   _stream_ptr(dev)), "rlx_loss_scale_rows")
+    return x
+
+
+class TurnScalePlan:
+    """Device plan of rlx_loss_scale_turn: int32 order | group_offsets | zero flag (0)."""
+
+    def __init__(self, order, offsets, device):
+        self.num_seq, self.num_groups = int(order.size), int(offsets.size - 1)
+        self.plan = _to_device_i32(order, offsets, [0], device=torch.device(device))
+        self.zero_flag = self.plan[-1:]
+
+
+def turn_level_scale_(loss_scales: torch.Tensor, response_mask: torch.Tensor, plan: TurnScalePlan) -> torch.Tensor:
+    """loss_scales[t] *= f32(T * |o_t| / sum_t |o_t|) per (trajectory, sub-trajectory) group, in place, one launch.  Returns the
+    plan's device zero flag (1: some group's mask total is 0 and was left unscaled) without reading it."""
+    dev = _dev(loss_scales, response_mask, plan.plan)
+    dt = _scaled_dtype(loss_scales, "turn_level_scale_")
+    if response_mask.dim() != 2 or loss_scales.dim() != 2 or tuple(loss_scales.shape) != tuple(response_mask.shape) \
+            or loss_scales.shape[0] != plan.num_seq:
+        raise RlxError(f"turn_level_scale_: loss_scales and response_mask must both be [num_seq = {plan.num_seq}, seq] "
+                       f"(got {tuple(loss_scales.shape)}, {tuple(response_mask.shape)})")
+    m = _as_u8(response_mask)
+    if m.data_ptr() % 4:
+        m = m.clone()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rlx_loss_scale_turn(loss_scales.data_ptr(), dt, m.data_ptr(), plan.plan.data_ptr(), plan.num_seq,
+                                                   plan.num_groups, loss_scales.shape[1], plan.zero_flag.data_ptr(),
+                                                   _stream_ptr(dev)), "rlx_loss_scale_turn")
+    return plan.zero_flag
