@@ -87,6 +87,8 @@ def act(policy, states: torch.Tensor, eps: torch.Tensor, rounding: bool = True):
     std = torch.exp(policy.actor_logstd.expand_as(mean))
     action = eps * std + mean
     logp = -((action - mean) ** 2) / (2 * std ** 2) - std.log() - LOG_SQRT_2PI
+    if not getattr(policy, "add_value_head", True):  # value-free policy: zeros, as OracleMLPPolicy.act
+        return action, logp, torch.zeros_like(logp[..., :1])
     mlp = policy.value_head.mlp
     value = (_mlp3(x, [mlp[0], mlp[2], mlp[4]], rounding) @ mlp[6].weight.double().t()).float()
     return action, logp, value

@@ -269,7 +269,7 @@ def validate_embodied_cfg(cfg):
 # Shape limits of the HIP kernels behind ``mlp_policy`` (this build's own check -- the reference's torch modules take any
 # width): the rollout launch and the fused optimizer step keep a row tile's activations in ONE LDS slab of 256 columns and the
 # first layer's weight tiles zero-padded to 64 inputs (csrc/ppo_step_common.h: HID = 256, Tiles::K1P = 64), and the head's
-# outputs in 16 accumulator columns (MAX_OUT = 16).  All of the reference's MLP configurations fit (obs_dim <= 42, act 8).
+# outputs in 16 accumulator columns (MAX_OUT = 16).  All of the reference's MLP configurations fit (obs_dim <= 42, act <= 9).
 MLP_KERNEL_LIMITS = {"hidden_dim": 256, "obs_dim_max": 64, "action_outputs_max": 16}
 
 

@@ -165,11 +165,13 @@ __device__ __forceinline__ void flush_rows(const float* X, float* __restrict__ d
 
 // obs-preprocess: the state rows themselves (mlp_policy.py:122-124); zero-pad the k tail and the rows past M.
 // states_copy: optional second destination (forward_inputs.states row of the trajectory buffer).
+// The k tail runs to Tiles::K1P, not round_up(D, KPAD): the first layer's GEMM always takes K1P / 32 k-steps, and a column it
+// reads that this launch did not write holds whatever an earlier workgroup left in LDS (0 * a stale Inf / NaN is NaN).
 template <int RT, int NW>
 __device__ __forceinline__ void load_states(const float* __restrict__ states, float* __restrict__ states_copy, int D,
                                             long long m0, long long M, float* X) {
     typedef Geo<RT, NW> G;
-    const int kp = round_up(D, KPAD);
+    constexpr int kp = Tiles::K1P;
     for (int i = threadIdx.x; i < G::BM * kp; i += G::NT) {
         const int r = i / kp, c = i % kp;
         const bool ok = c < D && m0 + r < M;

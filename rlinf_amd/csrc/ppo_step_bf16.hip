@@ -194,7 +194,7 @@ struct StatesB {
     }
     __device__ __forceinline__ void commit(const float* __restrict__ states, float* __restrict__ states_copy, int D, long long m0,
                                            long long M, __bf16* Xb) const {
-        const int kp = round_up(D, KPAD), nfloat = valid_floats(D, m0, M), nfull4 = nfloat >> 2, rem = nfloat & 3;
+        const int nfloat = valid_floats(D, m0, M), nfull4 = nfloat >> 2, rem = nfloat & 3;
         const float inv_d = 1.f / (float)D;
         auto row_of = [&](int e) {  // e / D for an element index e < 4096: the float quotient is off by far less than one
             int r = (int)(((float)e + 0.5f) * inv_d);
@@ -222,7 +222,9 @@ struct StatesB {
             Xb[r * XSB + (e - r * D)] = (__bf16)tail;
             if (copy) copy[e] = tail;
         }
-        const int padc = kp - D;  // the zero columns behind every row (the k tail of the first layer)
+        // the zero columns behind every row: the whole k tail the first layer's GEMM reads (Tiles::K1P / 32 k-steps, whatever
+        // round_up(D, KPAD) is), so that no column is left holding what an earlier workgroup wrote to this LDS (0 * a stale Inf / NaN is NaN)
+        const int padc = Tiles::K1P - D;
         for (int i = threadIdx.x; i < G::BM * padc; i += G::NT) Xb[(i / padc) * XSB + D + i % padc] = (__bf16)0.f;
     }
     // after an LDS barrier behind commit()

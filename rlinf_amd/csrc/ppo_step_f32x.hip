@@ -220,29 +220,30 @@ __device__ __forceinline__ float dtanh_x(__bf16 hi, __bf16 mid, __bf16 lo) {
     return fsub(1.f, fmul(h, h));
 }
 
-// obs-preprocess into the three slab planes (k tail and rows past M zero); issue / commit split as in StatesB
+// obs-preprocess into the three slab planes (k tail and rows past M zero); issue / commit split as in StatesB.  The k tail runs
+// to Tiles::K1P, the k-steps the first layer's GEMM takes whatever D is: a column left unwritten would hold what an earlier
+// workgroup wrote to this LDS (0 * a stale Inf / NaN is NaN).
 template <int RT, int NW>
 struct StatesX {
     typedef GeoX<RT, NW> G;
     static_assert(Tiles::K1P == 64, "one pass per lane assumes a 64-wide padded first layer");
     static constexpr int UB = G::BM * Tiles::K1P / G::NT;
+    static constexpr int KW = Tiles::K1P;  // columns written per row
     float x[UB];
     __device__ __forceinline__ void issue(const float* __restrict__ states, int D, long long m0, long long M) {
-        const int kp = round_up(D, KPAD);
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
-            const int i = min((int)threadIdx.x + u * G::NT, G::BM * kp - 1);
-            const int r = i / kp, c = i % kp;
+            const int i = min((int)threadIdx.x + u * G::NT, G::BM * KW - 1);
+            const int r = i / KW, c = i % KW;
             x[u] = states[(size_t)min(m0 + r, M - 1) * D + min(c, D - 1)];
         }
     }
     __device__ __forceinline__ void commit(float* __restrict__ states_copy, int D, long long m0, long long M, __bf16* Xb) const {
-        const int kp = round_up(D, KPAD);
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
             const int i = (int)threadIdx.x + u * G::NT;
-            if (i >= G::BM * kp) continue;
-            const int r = i / kp, c = i % kp;
+            if (i >= G::BM * KW) continue;
+            const int r = i / KW, c = i % KW;
             const bool ok = c < D && m0 + r < M;
             if (ok && states_copy) states_copy[(size_t)(m0 + r) * D + c] = x[u];
             const float v = ok ? x[u] : 0.f;
