@@ -1,22 +1,26 @@
 #!/usr/bin/env python
 """Headline benchmark: ManiSkill-shaped 1024-env PPO actor-learner loop on MI355X (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: one rank per GPU.  Launched by torch.distributed.run -- RANK / LOCAL_RANK / WORLD_SIZE from the env -- or, from a bare
     shell, by this script itself: without a torchrun environment `--gpus N` spawns the N ranks and rank 0 prints the line.)
+
+A plain run does only what the headline needs: it sets up, runs W warm-up and K timed steps, writes --dump-outputs if asked and
+prints the line.  Everything else it can measure -- the other scaling regime, the roofline probes, the variants, the CPU baselines,
+the per-kernel table -- runs only under --full (the --no-* options then leave parts of it out).
 
 One "step" = one full iteration of the hot path over one batch of synthetic input, through the reference-shaped
 runner/workers: rollout (T = 128 policy steps on B = 1024 envs incl. bootstrap-value forwards and the closing value
 row) -> GAE advantages/returns -> shuffle -> update_epoch x minibatches of fused forward / PPO loss / backward /
 clip+AdamW (8 x 16 = 128 optimizer steps at global_batch 8192).  Inputs (the synthetic env tensors) are resident in
 HBM before the timed region.  Total work is fixed as N grows (envs and the global minibatch are sharded over ranks):
-strong scaling -- the headline `value`, as north_star asks.  At N > 1 the same line also carries `weak_scaling` (1024 envs and
-8192 minibatch rows PER GPU: the regime where more GPUs buy throughput on a loop this short) and `transports` (the timed region
+strong scaling -- the headline `value`, as north_star asks.  At N > 1 the same line also carries `transports` (the timed region
 once per gradient transport: RCCL between eager launches first -- the most conservative path --, then the hand-written xGMI exchange
-and RCCL inside the captured update graph; the headline is the fastest one and says which).
+and RCCL inside the captured update graph; the headline is the fastest one and says which) and, with --full, `weak_scaling` (1024
+envs and 8192 minibatch rows PER GPU: the regime where more GPUs buy throughput on a loop this short) with its transports.
 Rank 0 prints ONE JSON line.
 
-Extra objects on that line (the roofline probes themselves live in tools/bench_roofline.py):
+Extra objects on that line under --full (the roofline probes themselves live in tools/bench_roofline.py):
   roofline      gae_scan (the kernel BASELINE.json grades against the HBM roofline), timed live with HIP events on the
                 launch stream at the scaled shape 65536 envs x 128 steps (the 1024 x 128 buffer is 2.2 MB and lives in
                 L2); algorithmic bytes = 17 B per env-step.
@@ -94,9 +98,6 @@ def build_runner(cfg, ctx, learner: str = "sync"):
     runner = EmbodiedRunner(cfg, actor, rollout, env)
     runner.init_workers()
     return runner
-
-
-from tools.bench_roofline import gae_roofline, token_tier_roofline  # noqa: E402  (the roofline probes: tools/bench_roofline.py)
 
 
 def _lib_handle():
@@ -529,11 +530,14 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="(kept for old command lines: one stream is the default now)")
     ap.add_argument("--learner", default="sync", choices=["sync", "async"],
                     help="async: AsyncPPOEmbodiedFSDPActor (decoupled actor-critic loss, SURVEY.md 8f-4) as the timed loop -- a variant "
-                         "line for traces and A/B runs, not the BASELINE.json configuration (the default run reports it under variants)")
+                         "line for traces and A/B runs, not the BASELINE.json configuration (a --full run reports it under variants)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="what `value` measures at N > 1: strong = 1024 envs in total (north_star's regime; the default), weak = "
-                         "1024 envs and an 8192-row minibatch per GPU.  The other regime rides along in the same line.")
+                         "1024 envs and an 8192-row minibatch per GPU.  With --full the other regime rides along in the same line.")
     ap.add_argument("--transports", default="auto", help="N > 1: comma list of gradient transports to time (xgmi, rccl); auto = both")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the other scaling regime (N > 1), the roofline probes, "
+                         "the 200-step sustained run, the variants, the per-kernel table, the scaling model and the CPU baselines")
     ap.add_argument("--variant-steps", type=int, default=50, help="timed iterations of each N = 1 variant line (f32, pipeline)")
     ap.add_argument("--no-variants", action="store_true", help="skip the exact-f32 and pipeline variant lines (N = 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -608,7 +612,7 @@ def main():
             "metric": "env_steps_per_sec", "value": head["env_steps_per_sec"], "unit": "env-steps/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": WORKLOAD.format(prec=PREC_TEXT[args.precision])
                                    + (" -- PER GPU (weak scaling)" if args.scaling == "weak" and args.gpus > 1 else ""),
                        "total_envs": head["total_envs"], "horizon": HORIZON, "global_batch": head["global_batch"],
@@ -638,10 +642,11 @@ def main():
                                        {"passed": False, "note": "no run used the hand-written exchange" + (
                                            " (asked for in " + ", ".join(asked_xgmi) + ": validation failed or RLX_GRAD_ALLREDUCE forced RCCL; those runs used RCCL)"
                                            if asked_xgmi else "")})
-            other = "weak" if args.scaling == "strong" else "strong"
-            ob = best(other)
-            line[f"{other}_scaling"] = None if ob is None else {k: ob[2][k] for k in (
-                "env_steps_per_sec", "ms_per_step", "ms_per_step_windows", "ppo_updates_per_sec", "total_envs", "global_batch", "grad_allreduce")}
+            if args.full:
+                other = "weak" if args.scaling == "strong" else "strong"
+                ob = best(other)
+                line[f"{other}_scaling"] = None if ob is None else {k: ob[2][k] for k in (
+                    "env_steps_per_sec", "ms_per_step", "ms_per_step_windows", "ppo_updates_per_sec", "total_envs", "global_batch", "grad_allreduce")}
             line["transports"] = {f"{rg}/{tr}": {k: v[k] for k in ("env_steps_per_sec", "ms_per_step", "grad_allreduce", "update_graph_replayed", "devices_seen", "done_at_s") if k in v}
                                   for (rg, tr), v in runs.items()}
             if errors:
@@ -664,7 +669,7 @@ def main():
         other_regime = "weak" if args.scaling == "strong" else "strong"
         # the headline regime opens with the most conservative path, so that SOME number exists before anything newer runs
         first = ["rccl-eager"] if (args.transports == "auto" and not forced and use_graph) else []
-        pairs = [(args.scaling, tr) for tr in first + names] + [(other_regime, tr) for tr in names]
+        pairs = [(args.scaling, tr) for tr in first + names] + ([(other_regime, tr) for tr in names] if args.full else [])
         current = {"pair": None}
 
         def emergency():
@@ -702,8 +707,10 @@ def main():
     for v in runs.values():
         v.pop("_outputs", None)
 
-    # ---- N = 1: the variant lines (own runners, same timing method), then the probes ---------------------------------------
-    if args.gpus == 1:
+    # ---- --full, N = 1: the variant lines (own runners, same timing method), then the probes -------------------------------
+    if args.full and args.gpus == 1:
+        from tools.bench_roofline import gae_roofline, token_tier_roofline
+
         def extra(key, fn):
             """The headline fields above are already measured: a failure in a secondary probe is reported in the line
             instead of costing it."""
@@ -777,7 +784,8 @@ def main():
                         "cpu_fastest_to_slowest_step": [round(line["value"] / cb["value_fastest_step"], 1), round(line["value"] / cb["value_slowest_step"], 1)],
                         "cpu_lower_to_upper_quartile_step": [round(line["value"] / cb["value_lower_quartile_step"], 1),
                                                              round(line["value"] / cb["value_upper_quartile_step"], 1)]}
-    elif ctx.rank == 0 and not args.no_roofline:
+    elif args.full and ctx.rank == 0 and not args.no_roofline:
+        from tools.bench_roofline import gae_roofline
         try:
             line["roofline"] = gae_roofline(dev, with_traffic=False)
         except Exception as e:  # noqa: BLE001

@@ -385,15 +385,15 @@ def test_one_rank_drives_the_real_rccl_branch(tmp_path, transport, graph):
 
 @pytest.mark.gpu
 def test_bench_self_launches_its_ranks_from_a_bare_shell(tmp_path):
-    """`python bench.py --gpus 2` WITHOUT a torchrun environment: bench.py spawns the two ranks itself, times every
+    """`python bench.py --gpus 2 --full` WITHOUT a torchrun environment: bench.py spawns the two ranks itself, times every
     (regime, transport) pair and rank 0 prints ONE JSON line with the strong-scaling headline, the weak-scaling object and the
     per-transport table.  (One-GPU box: both ranks share the device -- RLX_BENCH_ALLOW_SHARED_GPU -- so gloo stands in for RCCL
     and the xGMI exchange runs with its hand-shake as a one-wave launch; the numbers mean nothing here, the launcher, the
     collective agreement on which runs exist and the line's schema are what is checked.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RLX_BENCH_ALLOW_SHARED_GPU="1", RLX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", RLX_XGMI_TIMEOUT_MS="60000")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-roofline",
-                        "--launch-timeout", "600"], env=env, capture_output=True, text=True, timeout=700)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-roofline", "--launch-timeout", "600"], env=env, capture_output=True, text=True, timeout=700)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]

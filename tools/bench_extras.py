@@ -90,7 +90,7 @@ def in_loop_kernels(precision: str, *, rows: int, envs: int, slabs: int, n_param
         env.pop(k, None)
     with tempfile.TemporaryDirectory(prefix="rlx_ilk_", dir=env["TMPDIR"]) as wd:
         cmd = [exe, "--kernel-trace", "-d", wd, "-o", "ilk", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3",
-               "--warmup", "2", "--precision", precision, "--no-cpu-baseline", "--no-roofline", "--no-variants", "--no-extras"]
+               "--warmup", "2", "--precision", precision]
         subprocess.run(cmd, env=env, cwd=wd, check=True, timeout=timeout_s, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(wd) for f in fs if f.endswith(".db")]
         if not dbs:
