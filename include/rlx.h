@@ -32,8 +32,9 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 114 /* 0.1.4: bumped whenever an argument struct or a signature changes (0.1.4: rlx_grpo_dynamic_adv,
-                           * rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries rlx_opd_*; round 6: rlx_xgmi_self_timing, the
+#define RLX_VERSION 115 /* 0.1.5: bumped whenever an argument struct or a signature changes (0.1.5: the development-build query removed;
+                           * 0.1.4: rlx_grpo_dynamic_adv, rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries
+                           * rlx_opd_*; round 6: rlx_xgmi_self_timing, the
                            * exchange inside rlx_xgmi_clip_adamw_step under sync_words; round 5: rlx_categorical_sample's
                            * softmax_lanes, rlx_adamw_params.sync_words; round 4's struct growth had left it at 100) */
 
@@ -48,10 +49,6 @@ enum rlx_status {
 };
 
 int rlx_version(void);
-/* 1: a development build (-DRLX_DEV_VARIANTS): the refuted / experimental kernel variants are compiled in and the RLX_* variant
- * environment switches are read; 0: the product build -- the measured-best path only, no variant switch is read, entry points asked
- * for a variant that is not compiled return RLX_ENOSYS. */
-int rlx_dev_variants(void);
 const char* rlx_last_error(void);
 
 /* sizeof() of the argument structs below as THIS library was compiled, in declaration order (gae_params, ppo_loss_params,
@@ -508,8 +505,7 @@ typedef struct rlx_ppo_step_args {
      *   `out` is then the rlx_dppo_out row.  The denominator of the actor loss -- the count of the behaviour mask -- depends on
      *   every row's forward, so the gradients of the ACTOR network (actor_logstd, backbone.*, actor_mean.*) leave in SUM form:
      *   multiply them by out[RLX_PPO_ACTOR_GRAD_SCALE] (rlx_clip_adamw_step does: rlx_adamw_params.deferred_scale).  The value
-     *   network's gradients are final as always.  The row-split bf16 launch (RLX_FUSED_ROWS) has no decoupled form: the
-     *   column-split one runs. */
+     *   network's gradients are final as always. */
     const struct rlx_decoupled_loss_params* decoupled;
     const float* proximal_logprobs;
     const float* versions;
@@ -743,8 +739,8 @@ int rlx_loss_scale_turn(void* loss_scales, int dtype, const uint8_t* response_ma
  *   places it) -> advantages, returns [bsz, seq] f32, un-normalised; gamma_lambda = (float)((double)gamma * gae_lambda).
  *   Normalisation is rlx_masked_standardize over the [bsz, seq] buffer with the loss mask (layout-agnostic).
  *   Rows of 16-byte aligned length (seq % 4 == 0, 16-byte aligned base pointers, seq <= 32768) run in registers, one wave per
- *   2048 tokens (csrc/gae_seq.hip); other shapes are staged through LDS.  `workspace` (rlx_gae_seq_workspace_bytes) is only read
- *   by a development variant of the long-row kernel; NULL is accepted otherwise.
+ *   2048 tokens (csrc/gae_seq.hip); other shapes are staged through LDS.  No kernel reads `workspace`
+ *   (rlx_gae_seq_workspace_bytes); NULL is accepted.
  * ------------------------------------------------------------------------------------------ */
 size_t rlx_gae_seq_workspace_bytes(int64_t bsz, int64_t seq);
 int rlx_gae_seq(const float* values, const float* rewards, float* advantages, float* returns, int64_t bsz, int64_t seq,

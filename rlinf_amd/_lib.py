@@ -12,7 +12,7 @@ import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# RLX_LIB_TAG=<tag>: load librlx_hip_<tag>.so, a variant build of the same sources (see csrc/build.py); dev sweeps only
+# RLX_LIB_TAG=<tag>: load librlx_hip_<tag>.so, another build of the same sources (see csrc/build.py) for same-box A/B runs
 _TAG = os.environ.get("RLX_LIB_TAG", "")
 LIB_PATH = os.path.join(_HERE, "librlx_hip" + ("_" + _TAG if _TAG else "") + ".so")
 
@@ -151,7 +151,6 @@ OPD_OUT_NAMES = {"loss": 0, "actor/policy_loss": 1, "actor/opd_reward": 2, "acto
 # name -> (restype, argtypes); kept in one table so tests can check it against include/rlx.h
 PROTOTYPES = {
     "rlx_version": (c_int, []),
-    "rlx_dev_variants": (c_int, []),
     "rlx_last_error": (c_char_p, []),
     "rlx_abi_struct_sizes": (c_int, [c_void_p, c_int]),
     "rlx_device_info": (c_int, [POINTER(c_int), POINTER(c_int)]),
@@ -296,7 +295,7 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 114:
+    if lib.rlx_version() < 115:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents

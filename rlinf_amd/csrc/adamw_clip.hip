@@ -685,12 +685,6 @@ __global__ __launch_bounds__(kOneThreads, 4) void reduce_clip_adamw_one_launch(O
     float* __restrict__ m = k.m;
     float* __restrict__ v = k.v;
     unsigned long long* sync = k.sync;
-#ifdef RLX_ONE_LAUNCH_STAMPS  /* timing experiment: wall-clock (100 MHz) stamps of every block behind the slots */
-#define RLX_OL_STAMP(q) do { if (threadIdx.x == 0) sync[kSyncSlot0 + kSlotStride * kMaxOneBlocks + 8 * blockIdx.x + (q)] = (unsigned long long)wall_clock64(); } while (0)
-#else
-#define RLX_OL_STAMP(q) do { } while (0)
-#endif
-    RLX_OL_STAMP(0);
     const unsigned e1 = (unsigned)__hip_atomic_load(&sync[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
     // sync[1], sticky: the exchange of an EARLIER launch on these words expired.  Every launch since then skips AS A WHOLE -- each
     // block reads the word here, before anything else, and it was set before this launch started -- so slots left behind by
@@ -815,7 +809,6 @@ __global__ __launch_bounds__(kOneThreads, 4) void reduce_clip_adamw_one_launch(O
     const bool publishes = !XCHG || is_owner || k.x.self_alias;
     double acc[1] = {(double)g4.x * (double)g4.x + (double)g4.y * (double)g4.y + (double)g4.z * (double)g4.z + (double)g4.w * (double)g4.w};
     if (!live) acc[0] = 0.0;
-    RLX_OL_STAMP(1);
     if (publishes) block_sum<1>(acc, s_red);
     else __syncthreads();
     if (threadIdx.x == 0 && publishes) {
@@ -837,7 +830,6 @@ __global__ __launch_bounds__(kOneThreads, 4) void reduce_clip_adamw_one_launch(O
             __hip_atomic_store(slot + 1, tag | (bits >> 32), __ATOMIC_RELAXED, SCOPE);
         }
     }
-    RLX_OL_STAMP(2);
     // Wave 0 polls for the block: lane L takes blocks L, L + 64, ... (up to 8), adds them in a fixed order (the same in every block ->
     // the same norm everywhere) and forms the step's scalars while its first polls are in flight (they cost ~1 us of f64 math on
     // one lane: in front of the publication they delayed every block's partial).  Measured alternatives, alternating in one
@@ -890,7 +882,6 @@ __global__ __launch_bounds__(kOneThreads, 4) void reduce_clip_adamw_one_launch(O
             }
         }
     }
-    RLX_OL_STAMP(3);
     double tot = 0.0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) tot += pv[u];
@@ -923,10 +914,7 @@ __global__ __launch_bounds__(kOneThreads, 4) void reduce_clip_adamw_one_launch(O
         if (k.state != nullptr) k.state[0] = steps_done, k.state[1] = skip ? 0 : 1;
         __hip_atomic_store(&sync[0], (unsigned long long)e1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    RLX_OL_STAMP(4);
     apply_seg_block(p, g, m, v, sb, p4, g4, m4, v4, coef, skip, sc, a, k.lay, k.tiles, s_t);
-    RLX_OL_STAMP(6);
-#undef RLX_OL_STAMP
 }
 
 // clip_adamw_kernel on the SegPlan's blocks (2048 parameters, hidden matrices as segments of their own -> the weight image's fast
@@ -1397,7 +1385,8 @@ using namespace rlx::opt;
 
 extern "C" size_t rlx_adamw_sync_words(int64_t n) {
     (void)n;
-    return (size_t)kSyncSlot0 + (size_t)kSlotStride * (size_t)kMaxOneBlocks + 8 * (size_t)kMaxOneBlocks;  // (+ room for the development stamps)
+    // (+ 8 words per block that once held timing stamps: kept so that the size the optimizer reports stays the same)
+    return (size_t)kSyncSlot0 + (size_t)kSlotStride * (size_t)kMaxOneBlocks + 8 * (size_t)kMaxOneBlocks;
 }
 
 extern "C" size_t rlx_adamw_workspace_bytes(int64_t n) {

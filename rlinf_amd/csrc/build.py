@@ -19,8 +19,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 INCLUDE = os.path.join(ROOT, "include")
-# dev: RLX_BUILD_TAG=nt builds librlx_hip_nt.so from objects in _build_nt (variant sweeps: pair with RLX_CXXFLAGS here and
-# RLX_LIB_TAG at run time); unset = the product library
+# RLX_BUILD_TAG=x builds librlx_hip_x.so from objects in _build_x, next to the product library, for same-box A/B runs of a
+# candidate change (pair with RLX_CXXFLAGS here and RLX_LIB_TAG at run time); unset = the product library
 _TAG = os.environ.get("RLX_BUILD_TAG", "")
 BUILD = os.path.join(HERE, "_build" + ("_" + _TAG if _TAG else ""))
 LIB = os.path.join(os.path.dirname(HERE), "librlx_hip" + ("_" + _TAG if _TAG else "") + ".so")
@@ -50,7 +50,7 @@ def _compile(src: str, force: bool, save_temps: bool) -> str:
         return obj
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
            "-Wall", "-Wno-unused-function", f"-I{INCLUDE}", f"-I{HERE}", "-c", src, "-o", obj]
-    cmd[1:1] = os.environ.get("RLX_CXXFLAGS", "").split()  # dev: extra -D switches for kernel variant sweeps
+    cmd[1:1] = os.environ.get("RLX_CXXFLAGS", "").split()  # extra compiler flags for a tagged A/B build
     if save_temps:
         cmd.insert(1, "-save-temps=obj")
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=BUILD)

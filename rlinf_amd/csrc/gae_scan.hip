@@ -30,13 +30,6 @@
 namespace rlx {
 namespace {
 
-#ifdef RLX_DEV_VARIANTS
-inline int dev_switch(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-#endif
-
 struct GaeArgs {
     const float* r;
     const float* v;      // nullptr => critic-free
@@ -325,218 +318,6 @@ __global__ __launch_bounds__(64 * NSEG) void gae_scan_c1(GaeArgs a) {
     flush_moments(mo, a.partials, s_red, grp);
 }
 
-#ifdef RLX_DEV_VARIANTS  // register-resident segment scans: bit-exact, measured slower (32-44 us against 28 us): development builds only
-// ------------------------------------------------------------------------------------------
-// Register-resident segmented scan (C == 1).  grid = ceil(B / (64*VEC)), block = 64*NSEG threads.
-//   Wave s of a block owns time segment [s*SEG, (s+1)*SEG) of 64*VEC envs and issues EVERY load of that segment
-//   up front (SEG rows x (r, V, done[, mask]) = 9 B per element live in VGPRs: SEG = 32, VEC = 4 -> 288 registers at
-//   one wave per SIMD, ~72 KB in flight per wave, 1 KiB per load instruction).  The recurrence then runs as a
-//   serial chain over the waves, latest segment first: wave s waits at a workgroup barrier for the accumulator
-//   g and hands it on through LDS (64*VEC floats -- the only LDS traffic), so every wave executes the reference's
-//   sequential recurrence with the true incoming g: results are bit-identical to the CPU loop, every byte is
-//   read once and written once, and while one wave computes and stores, the later waves' loads are still landing.
-// ------------------------------------------------------------------------------------------
-// Buffer (SRSRC) addressing: descriptor built from kernargs only (provably wave-uniform: no waterfall loops), the
-// per-lane part is one 32-bit voffset shared by every access, the row is a scalar soffset -- no per-lane 64-bit
-// address exists anywhere, which is what lets SEG x VEC x 9 bytes of segment data own the register file.
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <int VEC, bool NT>
-__device__ __forceinline__ void bld(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, float (&out)[VEC]) {
-    constexpr int aux = NT ? 2 : 0;
-    if constexpr (VEC == 1) {
-        out[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, aux));
-    } else if constexpr (VEC == 2) {
-        const u32x2 x = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, aux);
-        out[0] = __uint_as_float(x[0]); out[1] = __uint_as_float(x[1]);
-    } else {
-        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, aux);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = __uint_as_float(x[k]);
-    }
-}
-template <int VEC, bool NT>
-__device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, const float (&in)[VEC]) {
-    constexpr int aux = NT ? 2 : 0;
-    if constexpr (VEC == 1) {
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(in[0]), rs, voff, soff, aux);
-    } else if constexpr (VEC == 2) {
-        u32x2 x; x[0] = __float_as_uint(in[0]); x[1] = __float_as_uint(in[1]);
-        __builtin_amdgcn_raw_buffer_store_b64(x, rs, voff, soff, aux);
-    } else {
-        u32x4 x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = __float_as_uint(in[k]);
-        __builtin_amdgcn_raw_buffer_store_b128(x, rs, voff, soff, aux);
-    }
-}
-template <int VEC, bool NT>
-__device__ __forceinline__ uint32_t bldb(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-    constexpr int aux = NT ? 2 : 0;
-    if constexpr (VEC == 1) return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, voff, soff, aux);
-    else if constexpr (VEC == 2) return (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rs, voff, soff, aux);
-    else return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, aux);
-}
-
-template <int VEC, int NSEG, int SEG, bool NT, bool CRITIC, bool MASK>
-__global__ __launch_bounds__(64 * NSEG) void gae_scan_regseg(GaeArgs a) {
-    __shared__ float s_g[64 * VEC];
-    __shared__ double s_red[5 * NSEG];
-    const int lane = threadIdx.x & 63;
-    const int seg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned e0 = ((unsigned)blockIdx.x * 64u + (unsigned)lane) * VEC;
-    const bool active = e0 < (unsigned)a.B;  // B % VEC == 0 (host-checked): a lane is all in or all out
-    const int T = a.T;
-    const unsigned B = (unsigned)a.B;
-    const int t_lo = seg * SEG;
-    const int t_hi = min(T, t_lo + SEG);
-    const unsigned nf = (unsigned)T * B * 4u, nf1 = (unsigned)(T + 1) * B * 4u;  // < 2^31 (host-checked)
-    const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.r), 0, (int)nf, 0x00020000);
-    const auto rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.v), 0, CRITIC ? (int)nf1 : 0, 0x00020000);
-    const auto rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.d), 0, (int)(nf1 / 4), 0x00020000);
-    const auto rs_m = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.m), 0, MASK ? (int)(nf / 4) : 0, 0x00020000);
-    const auto rs_adv = __builtin_amdgcn_make_buffer_rsrc(a.adv, 0, (int)nf, 0x00020000);
-    const auto rs_ret = __builtin_amdgcn_make_buffer_rsrc(a.ret, 0, (int)nf, 0x00020000);
-    // inactive lanes (e0 >= B) park their offset past every buffer: hardware bounds-checking returns 0 / drops stores
-    const unsigned vo4 = active ? e0 * 4u : 0x7fffffffu, vo1 = active ? e0 : 0x7fffffffu;
-
-    float r[SEG][VEC], v[SEG][VEC], vtop[VEC];
-    uint32_t dn[SEG], mk[SEG];
-    // rows past the end of a ragged last segment re-load row T-1 (valid memory, value unused): a clamped
-    // address keeps the loads branch-free, a per-row predicate would make hipcc drain vmcnt(0) per row
-#pragma unroll
-    for (int u = SEG - 1; u >= 0; --u) {  // latest row first: that is the order the recurrence consumes them
-        const unsigned t = (unsigned)min(t_lo + u, T - 1);
-        bld<VEC, NT>(rs_r, vo4, t * B * 4u, r[u]);
-        if constexpr (CRITIC) bld<VEC, NT>(rs_v, vo4, t * B * 4u, v[u]);
-        dn[u] = bldb<VEC, NT>(rs_d, vo1, (t + 1) * B);
-        if constexpr (MASK) mk[u] = bldb<VEC, NT>(rs_m, vo1, t * B);
-        else mk[u] = 0x01010101u;
-    }
-    if constexpr (CRITIC) bld<VEC, false>(rs_v, vo4, (unsigned)min(t_hi, T) * B * 4u, vtop);
-
-    Moments mo;
-    for (int s = NSEG - 1; s >= 0; --s) {
-        if (s == seg && active && t_hi > t_lo) {
-            float g[VEC], vnext[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                g[k] = (t_hi == T) ? 0.f : s_g[lane * VEC + k];
-                vnext[k] = CRITIC ? vtop[k] : 0.f;
-            }
-#pragma unroll
-            for (int u = SEG - 1; u >= 0; --u) {
-                if (t_lo + u < t_hi) {  // wave-uniform
-                    float adv[VEC], ret[VEC];
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        const bool done = (dn[u] >> (8 * k)) & 0xffu;
-                        const bool on = (mk[u] >> (8 * k)) & 0xffu;
-                        const float vk = CRITIC ? v[u][k] : 0.f;
-                        gae_step(r[u][k], vk, vnext[k], done ? 0.f : 1.f, CRITIC, a.gamma, a.gl, g[k], adv[k], ret[k]);
-                        mo.add(adv[k], ret[k], on);
-                        vnext[k] = vk;
-                    }
-                    const unsigned row = (unsigned)(t_lo + u) * B * 4u;
-                    bst<VEC, NT>(rs_adv, vo4, row, adv);
-                    bst<VEC, NT>(rs_ret, vo4, row, ret);
-                }
-            }
-            if (s > 0) {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) s_g[lane * VEC + k] = g[k];
-            }
-        }
-        if (NSEG > 1 && s > 0) __syncthreads();
-    }
-    flush_moments(mo, a.partials, s_red);
-}
-
-// ------------------------------------------------------------------------------------------
-// Register-resident segments with an EARLY hand-off (C == 1, one env per lane).  grid = ceil(B / 64), block = 64 * NSEG threads.
-//   Why: a wave can have at most 64 vector-memory operations outstanding (vmcnt is 6 bits), so the one-wave-per-env-group
-//   streaming scan caps the bytes in flight at B x 256 B whatever its register batches hold -- 16.8 MB at 65536 envs, about what
-//   5.3 TB/s x 3 us needs and no more.  More waves per env group is the only way to put more requests in flight.
-//   How: wave s owns the time segment [s * SEG, (s + 1) * SEG) and requests ALL its rows up front (r, V, done: 3 * SEG loads).
-//   The recurrence needs the accumulator g from the later segment; gae_scan_regseg passes it down a serial chain in which
-//   every wave computes AND stores before the next one starts.  Here the chain carries ONLY the recurrence -- SEG fused
-//   multiply-add-class steps from registers, no stores -- then every wave runs its full pass (recurrence again, moments, stores)
-//   CONCURRENTLY with its true incoming g.  Same operations in the same order as the sequential loop: bit-identical results.
-// ------------------------------------------------------------------------------------------
-template <int NSEG, int SEG, bool NT, bool CRITIC, bool MASK>
-__global__ __launch_bounds__(64 * NSEG) void gae_scan_handoff(GaeArgs a) {
-    __shared__ float s_gin[NSEG][64];
-    __shared__ double s_red[5 * NSEG];
-    const int lane = threadIdx.x & 63;
-    const int seg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const unsigned e0 = (unsigned)blockIdx.x * 64u + (unsigned)lane;
-    const bool active = e0 < (unsigned)a.B;
-    const int T = a.T;
-    const unsigned B = (unsigned)a.B;
-    const int t_lo = seg * SEG;
-    const int t_hi = min(T, t_lo + SEG);
-    const unsigned nf = (unsigned)T * B * 4u, nf1 = (unsigned)(T + 1) * B * 4u;  // < 2^31 (host-checked)
-    const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.r), 0, (int)nf, 0x00020000);
-    const auto rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.v), 0, CRITIC ? (int)nf1 : 0, 0x00020000);
-    const auto rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.d), 0, (int)(nf1 / 4), 0x00020000);
-    const auto rs_m = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.m), 0, MASK ? (int)(nf / 4) : 0, 0x00020000);
-    const auto rs_adv = __builtin_amdgcn_make_buffer_rsrc(a.adv, 0, (int)nf, 0x00020000);
-    const auto rs_ret = __builtin_amdgcn_make_buffer_rsrc(a.ret, 0, (int)nf, 0x00020000);
-    const unsigned vo4 = active ? e0 * 4u : 0x7fffffffu, vo1 = active ? e0 : 0x7fffffffu;
-
-    float r[SEG][1], v[SEG][1], vtop[1] = {0.f};
-    uint32_t dn[SEG], mk[SEG];
-#pragma unroll
-    for (int u = SEG - 1; u >= 0; --u) {  // latest row first: the order the recurrence consumes them
-        const unsigned t = (unsigned)min(t_lo + u, T - 1);
-        bld<1, NT>(rs_r, vo4, t * B * 4u, r[u]);
-        if constexpr (CRITIC) bld<1, NT>(rs_v, vo4, t * B * 4u, v[u]);
-        dn[u] = bldb<1, NT>(rs_d, vo1, (t + 1) * B);
-        if constexpr (MASK) mk[u] = bldb<1, NT>(rs_m, vo1, t * B);
-        else mk[u] = 1u;
-    }
-    if constexpr (CRITIC) bld<1, false>(rs_v, vo4, (unsigned)min(t_hi, T) * B * 4u, vtop);
-
-    // ---- the chain: recurrence only, latest segment first; s_gin[s] = the accumulator segment s hands to segment s - 1 ----
-    for (int s = NSEG - 1; s >= 1; --s) {
-        if (s == seg) {
-            float g = (s == NSEG - 1 || t_hi >= T) ? 0.f : s_gin[s + 1 < NSEG ? s + 1 : s][lane];
-            float vnext = CRITIC ? vtop[0] : 0.f, adv, ret;
-#pragma unroll
-            for (int u = SEG - 1; u >= 0; --u) {
-                if (t_lo + u < t_hi) {
-                    const float vk = CRITIC ? v[u][0] : 0.f;
-                    gae_step(r[u][0], vk, vnext, (dn[u] & 0xffu) ? 0.f : 1.f, CRITIC, a.gamma, a.gl, g, adv, ret);
-                    vnext = vk;
-                }
-            }
-            s_gin[s][lane] = g;
-        }
-        __syncthreads();
-    }
-    // ---- the full pass, all segments at once -------------------------------------------------------------------------------
-    Moments mo;
-    if (active && t_hi > t_lo) {
-        float g = (seg == NSEG - 1 || t_hi >= T) ? 0.f : s_gin[seg + 1 < NSEG ? seg + 1 : seg][lane];
-        float vnext = CRITIC ? vtop[0] : 0.f;
-#pragma unroll
-        for (int u = SEG - 1; u >= 0; --u) {
-            if (t_lo + u < t_hi) {  // wave-uniform
-                float adv[1], ret[1];
-                const float vk = CRITIC ? v[u][0] : 0.f;
-                gae_step(r[u][0], vk, vnext, (dn[u] & 0xffu) ? 0.f : 1.f, CRITIC, a.gamma, a.gl, g, adv[0], ret[0]);
-                mo.add(adv[0], ret[0], (mk[u] & 0xffu) != 0);
-                vnext = vk;
-                const unsigned row = (unsigned)(t_lo + u) * B * 4u;
-                bst<1, NT>(rs_adv, vo4, row, adv);
-                bst<1, NT>(rs_ret, vo4, row, ret);
-            }
-        }
-    }
-    flush_moments(mo, a.partials, s_red);
-}
-
-#endif  // RLX_DEV_VARIANTS
 // ------------------------------------------------------------------------------------------
 // Generic time-chunk layout (C > 1): one lane per env, sequential, strided addressing.
 //   time step t = k*C + c  ->  element ((k*B + b)*C + c); dones use flat rows shifted by C-1
@@ -748,23 +529,15 @@ int dispatch_c1(const GaeArgs& a, hipStream_t s, int nblk, int rows = 8, bool nt
     const bool critic = a.v != nullptr, mask = a.m != nullptr;
     if constexpr (NSEG == 1) {  // streaming-scan tuning variants (critic, no mask: the bench / sweep configuration)
         if (critic && !mask) {
-#ifdef RLX_DEV_VARIANTS
-            if (rows == 16) return nt ? launch_c1<1, 1, 16, true, true, false>(a, s, nblk) : launch_c1<1, 1, 16, false, true, false>(a, s, nblk);
-            if (rows == 32) return nt ? launch_c1<1, 1, 32, true, true, false>(a, s, nblk) : launch_c1<1, 1, 32, false, true, false>(a, s, nblk);
-            if (rows == 64 && nt && dev_switch("RLX_GAE_PAIR", 1) == 0) return launch_c1<1, 1, 64, true, true, false>(a, s, nblk);
-            if (rows == 64 && !nt) return launch_c1<1, 1, 64, false, true, false>(a, s, nblk);
-            if (rows == 128) return nt ? launch_c1<1, 1, 128, true, true, false>(a, s, nblk) : launch_c1<1, 1, 128, false, true, false>(a, s, nblk);
-            if (nt && rows != 64) return launch_c1<1, 1, 8, true, true, false>(a, s, nblk);
-#else
             if (rows != 64 && (rows != 8 || nt)) {
-                set_error("rlx_gae_scan: this streaming tuning variant (rows %d, nt %d) is compiled into development builds only", rows, (int)nt);
+                set_error("rlx_gae_scan: the streaming tuning variant rows %d, nt %d was measured slower and removed "
+                          "(profiles/r01_gae_hbm_sweep_stream.txt)", rows, (int)nt);
                 return RLX_ENOSYS;
             }
             if (rows == 64 && !nt) {
-                set_error("rlx_gae_scan: the 64-row streaming scan is compiled with non-temporal accesses only (development builds hold the other)");
+                set_error("rlx_gae_scan: the 64-row streaming scan exists with non-temporal accesses only");
                 return RLX_ENOSYS;
             }
-#endif
             if (rows == 64) return launch_c1<1, 1, 64, true, true, false, true>(a, s, nblk);  // the measured-best streaming scan (auto at HBM sizes)
         }
         // ... and with a loss mask (round 6): the same streaming form at 32 rows per register batch -- the mask byte is a fourth
@@ -776,35 +549,6 @@ int dispatch_c1(const GaeArgs& a, hipStream_t s, int nblk, int rows = 8, bool nt
     if (!critic && mask) return launch_c1<1, NSEG, 8, false, false, true>(a, s, nblk);
     return launch_c1<1, NSEG, 8, false, false, false>(a, s, nblk);
 }
-
-#ifdef RLX_DEV_VARIANTS
-template <int VEC, int NSEG, int SEG, bool NT>
-int launch_regseg(const GaeArgs& a, hipStream_t s) {
-    const int nblk = ceil_div(a.B, 64 * VEC);
-    const bool critic = a.v != nullptr, mask = a.m != nullptr;
-    const dim3 g(nblk), b(64 * NSEG);
-    if (critic && !mask) hipLaunchKernelGGL((gae_scan_regseg<VEC, NSEG, SEG, NT, true, false>), g, b, 0, s, a);
-    else if (critic && mask) hipLaunchKernelGGL((gae_scan_regseg<VEC, NSEG, SEG, NT, true, true>), g, b, 0, s, a);
-    else if (!critic && mask) hipLaunchKernelGGL((gae_scan_regseg<VEC, NSEG, SEG, NT, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((gae_scan_regseg<VEC, NSEG, SEG, NT, false, false>), g, b, 0, s, a);
-    RLX_LAUNCH_CHECK();
-    return RLX_OK;
-}
-
-// register-resident segments of SEG steps: NSEG = ceil(T / SEG) waves per block (at most 16 waves)
-template <int VEC, int SEG, bool NT>
-int dispatch_regseg(const GaeArgs& a, hipStream_t s) {
-    const int nseg = ceil_div(a.T, SEG);
-    if (nseg <= 1) return launch_regseg<VEC, 1, SEG, NT>(a, s);
-    if (nseg <= 2) return launch_regseg<VEC, 2, SEG, NT>(a, s);
-    if (nseg <= 4) return launch_regseg<VEC, 4, SEG, NT>(a, s);
-    if (nseg <= 8) return launch_regseg<VEC, 8, SEG, NT>(a, s);
-    if (nseg <= 16) return launch_regseg<VEC, 16, SEG, NT>(a, s);
-    set_error("rlx_gae_scan: the register-resident variant needs T <= %d (T=%d)", 16 * SEG, a.T);
-    return RLX_EINVAL;
-}
-
-#endif  // RLX_DEV_VARIANTS
 
 int standardize_grid(size_t n, int u, int per_cu) {
     const long long want = (long long)((n / 4 + 256 * u - 1) / (256 * u));
@@ -896,56 +640,12 @@ extern "C" int rlx_gae_scan(const float* rewards, const float* values, const uin
             nt_sel = true;
         }
         const bool regseg = (p->variant >> 26) & 1;  // register-resident 32-step segments, serial carry chain
-        const bool handoff = (p->variant >> 28) & 1;  // register-resident segments, early hand-off (gae_scan_handoff)
-#ifndef RLX_DEV_VARIANTS
+        const bool handoff = (p->variant >> 28) & 1;  // register-resident segments, early hand-off
         if (handoff || regseg) {
-            set_error("rlx_gae_scan: the register-resident segment variants are compiled into development builds only (-DRLX_DEV_VARIANTS)");
+            set_error("rlx_gae_scan: the register-resident segment variants (variant bits 26 and 28) were measured slower and removed "
+                      "(profiles/r01_gae_hbm_sweep_regseg.txt, profiles/r03_gae_handoff_sweep_*.txt)");
             return RLX_ENOSYS;
         }
-        {
-#else
-        if (handoff) {
-            RLX_REQUIRE((unsigned long long)(a.T + 1) * (unsigned long long)batch * 4ull < (1ull << 31),
-                        "rlx_gae_scan: the hand-off variant addresses rows through 32-bit buffer offsets: (T+1)*B*4 must stay below 2 GiB");
-            const int seg = 16 << ((p->variant >> 29) & 3);  // 16, 32, 64
-            RLX_REQUIRE(seg <= 64, "rlx_gae_scan: hand-off segment of %d steps", seg);
-            const int ns = ceil_div(a.T, seg);
-            RLX_REQUIRE(ns >= 1 && ns <= 8, "rlx_gae_scan: hand-off variant with %d-step segments needs T <= %d (T=%d)", seg, 8 * seg, a.T);
-            const bool critic = a.v != nullptr, mask = a.m != nullptr;
-            nblk = ceil_div(batch, 64);
-#define RLX_HANDOFF(NS, SG)                                                                                                        \
-            do {                                                                                                                       \
-                if (critic && !mask) { if (nt) hipLaunchKernelGGL((gae_scan_handoff<NS, SG, true, true, false>), dim3(nblk), dim3(64 * NS), 0, s, a);   \
-                                       else hipLaunchKernelGGL((gae_scan_handoff<NS, SG, false, true, false>), dim3(nblk), dim3(64 * NS), 0, s, a); }    \
-                else if (critic) hipLaunchKernelGGL((gae_scan_handoff<NS, SG, false, true, true>), dim3(nblk), dim3(64 * NS), 0, s, a);                \
-                else if (mask) hipLaunchKernelGGL((gae_scan_handoff<NS, SG, false, false, true>), dim3(nblk), dim3(64 * NS), 0, s, a);                 \
-                else hipLaunchKernelGGL((gae_scan_handoff<NS, SG, false, false, false>), dim3(nblk), dim3(64 * NS), 0, s, a);                          \
-            } while (0)
-            const int nsp = ns <= 1 ? 1 : ns <= 2 ? 2 : ns <= 4 ? 4 : 8;
-            if (seg == 64) { if (nsp == 1) RLX_HANDOFF(1, 64); else if (nsp == 2) RLX_HANDOFF(2, 64); else if (nsp == 4) RLX_HANDOFF(4, 64); else RLX_HANDOFF(8, 64); }
-            else if (seg == 32) { if (nsp == 1) RLX_HANDOFF(1, 32); else if (nsp == 2) RLX_HANDOFF(2, 32); else if (nsp == 4) RLX_HANDOFF(4, 32); else RLX_HANDOFF(8, 32); }
-            else { if (nsp == 1) RLX_HANDOFF(1, 16); else if (nsp == 2) RLX_HANDOFF(2, 16); else if (nsp == 4) RLX_HANDOFF(4, 16); else RLX_HANDOFF(8, 16); }
-#undef RLX_HANDOFF
-            RLX_LAUNCH_CHECK();
-        } else if (regseg) {
-            RLX_REQUIRE(vec == 1 || vec == 2 || vec == 4, "rlx_gae_scan: regseg vec=%d", vec);
-            RLX_REQUIRE(batch % vec == 0, "rlx_gae_scan: regseg vec=%d needs batch %% vec == 0 (batch=%d)", vec, batch);
-            RLX_REQUIRE((unsigned long long)(a.T + 1) * (unsigned long long)batch * 4ull < (1ull << 31),
-                        "rlx_gae_scan: regseg addresses rows through 32-bit buffer offsets: (T+1)*B*4 must stay below 2 GiB");
-            const uintptr_t al = (uintptr_t)rewards | (uintptr_t)values | (uintptr_t)advantages | (uintptr_t)returns;
-            RLX_REQUIRE(vec == 1 || al % (4 * vec) == 0, "rlx_gae_scan: regseg vec=%d needs %d-byte aligned buffers", vec, 4 * vec);
-            nblk = ceil_div(batch, 64 * vec);
-            const bool seg16 = (p->variant >> 27) & 1;  // 16-step segments (twice the waves, half the registers)
-            int rc;
-            // VEC = 4 keeps 16-step segments only: 32 x 4 x 9 B = 288 data registers makes hipcc spill
-            if (vec == 4) rc = nt ? dispatch_regseg<4, 16, true>(a, s) : dispatch_regseg<4, 16, false>(a, s);
-            else if (vec == 2 && seg16) rc = nt ? dispatch_regseg<2, 16, true>(a, s) : dispatch_regseg<2, 16, false>(a, s);
-            else if (vec == 2) rc = nt ? dispatch_regseg<2, 32, true>(a, s) : dispatch_regseg<2, 32, false>(a, s);
-            else if (seg16) rc = nt ? dispatch_regseg<1, 16, true>(a, s) : dispatch_regseg<1, 16, false>(a, s);
-            else rc = nt ? dispatch_regseg<1, 32, true>(a, s) : dispatch_regseg<1, 32, false>(a, s);
-            if (rc != RLX_OK) return rc;
-        } else {
-#endif
         if (vec != 1) {
             set_error("rlx_gae_scan: vec=%d is compiled out (no gain on MI355X, see profiles/r01_gae_variant_sweep.txt)", vec);
             return RLX_ENOSYS;
@@ -964,7 +664,6 @@ extern "C" int rlx_gae_scan(const float* rewards, const float* values, const uin
             case 16: rc = dispatch_c1<16>(a, s, nblk); break;
         }
         if (rc != RLX_OK) return rc;
-        }
     }
     if (p->normalize_advantages) {
         launch_standardize(advantages, n, a.partials, nblk, 0, p->norm_eps, s);

@@ -784,7 +784,7 @@ extern "C" int rlx_mlp_rollout_step(const rlx_rollout_step* r, rlx_stream_t stre
     a.stamps = g_timing_buffer;
     a.params = r->params; a.tiles = r->tiles; a.lay = *r->layout; a.states = r->states; a.eps = r->eps; a.M = r->m;
     a.action = r->action; a.logprob = r->logprob; a.value = r->value; a.states_copy = r->states_copy;
-    const int bm = r->bf16 ? rollout_bm_bf16() : 16;  // rows per workgroup
+    const int bm = 16;  // rows per workgroup
     a.tiles_policy = ceil_div(r->m, bm);
     int tv[2] = {0, 0};
     for (int k = 0; k < r->n_value_jobs; ++k) {
@@ -806,22 +806,8 @@ extern "C" int rlx_mlp_rollout_step(const rlx_rollout_step* r, rlx_stream_t stre
     if (r->bf16) return launch_rollout_bf16(a, blocks, st);
     if (f32_split()) return launch_rollout_f32x(a, blocks, st);
     const size_t lds = Geo<1, 8>::LDS_BYTES;
-    const int v = dev_variant("RLX_ROLLOUT_PD", 2);
-#define RLX_LAUNCH_ROLLOUT(PDV)                                                                 \
-    do {                                                                                        \
-        if (int rc = set_lds(rollout_step_kernel<PDV>, lds)) return rc;                         \
-        hipLaunchKernelGGL(rollout_step_kernel<PDV>, dim3(blocks), dim3(512), lds, st, a);      \
-    } while (0)
-#ifdef RLX_DEV_VARIANTS
-    if (v == 1) RLX_LAUNCH_ROLLOUT(1);
-    else if (v == 4) RLX_LAUNCH_ROLLOUT(4);
-    else if (v == 8) RLX_LAUNCH_ROLLOUT(8);
-    else RLX_LAUNCH_ROLLOUT(2);
-#else
-    (void)v;
-    RLX_LAUNCH_ROLLOUT(2);
-#endif
-#undef RLX_LAUNCH_ROLLOUT
+    if (int rc = set_lds(rollout_step_kernel<2>, lds)) return rc;
+    hipLaunchKernelGGL(rollout_step_kernel<2>, dim3(blocks), dim3(512), lds, st, a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
@@ -862,7 +848,7 @@ extern "C" int rlx_ppo_step_slabs_for(const rlx_mlp_layout* lay, int64_t m, int3
 
 extern "C" size_t rlx_ppo_step_workspace_bytes(const rlx_mlp_layout* lay, int64_t m) {
     if (!lay || m <= 0) return 256;
-    return std::max({plan_step(lay, m, false).bytes, plan_step(lay, m, true).bytes, plan_step(lay, m, true, true).bytes});  // any launch fits
+    return std::max(plan_step(lay, m, false).bytes, plan_step(lay, m, true).bytes);  // any launch fits
 }
 
 extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
@@ -887,8 +873,7 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
         RLX_REQUIRE(dp->proximal_mode != RLX_PROX_GIVEN || s->proximal_logprobs, "rlx_ppo_step: proximal_mode GIVEN without proximal_logprobs");
         RLX_REQUIRE(dp->proximal_mode != RLX_PROX_FROM_VERSIONS || s->versions, "rlx_ppo_step: proximal_mode FROM_VERSIONS without versions");
     }
-    const bool rows = bf16 && dp == nullptr && fused_rows_bf16() && fused_rows_eligible(lay, p);
-    const StepPlan pl = plan_step(&lay, s->m, bf16, rows);
+    const StepPlan pl = plan_step(&lay, s->m, bf16);
     RLX_REQUIRE(s->slabs == pl.slabs, "rlx_ppo_step: grads holds %d slabs, rlx_ppo_step_slabs() says %d", s->slabs, pl.slabs);
     if (s->workspace_bytes < pl.bytes) {
         set_error("rlx_ppo_step: workspace %zu < %zu bytes", s->workspace_bytes, pl.bytes);
@@ -898,8 +883,8 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
     char* ws = static_cast<char*>(s->workspace);
     StepArgs a{};
     a.stamps = g_timing_buffer;
-    a.merged_loss_pass = dev_variant("RLX_FUSED_MERGED", 1);
-    a.xcd_rows = dev_variant("RLX_FUSED_XCD_ROWS", 0);  // measured: no effect (see the kernel), identity kept
+    a.merged_loss_pass = 1;
+    a.xcd_rows = 0;  // measured: no effect (see the kernel), identity kept
     a.params = s->params; a.lay = lay; a.states = s->states; a.action = s->action; a.old_logprobs = s->old_logprobs;
     a.advantages = s->advantages; a.prev_values = s->prev_values; a.returns = s->returns; a.loss_mask = s->loss_mask;
     a.loss_mask_sum = s->loss_mask_sum; a.M = s->m; a.p = p; a.grad_out = s->grad_out;
@@ -917,11 +902,7 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
     d.M = s->m; d.rows_per_slab = pl.rows_per_slab; d.slabs = pl.slabs; d.tiles = pl.loss_slots; d.head_parts = pl.head_parts;
     d.head_stride = pl.head_stride;
     d.gemm_items = pl.slabs * 20; d.grads = s->grads; d.p = p; d.has_mask = s->loss_mask != nullptr;
-#ifdef RLX_DEV_VARIANTS  // timing tool only (the sums come out multiplied): not reachable in the product build
-    d.repeat = std::max(1, dev_variant("RLX_DW_REPEAT", 1));
-#else
     d.repeat = 1;
-#endif
     d.has_msum = s->loss_mask_sum != nullptr; d.out = s->out;
     d.decoupled = dp != nullptr; d.dec_use_threshold = dp != nullptr && dp->use_behave_threshold != 0;
     const int dw_blocks = round_up(d.gemm_items, 8) + pl.slabs * 2 + 1;
@@ -933,7 +914,7 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
             a.tiles = static_cast<const float*>(tiles);
             if (int rc = pack_tiles_bf16(s->params, lay, tiles, st)) return rc;
         }
-        return launch_step_bf16(a, d, ws + pl.off_st, pl.tiles, dw_blocks, lay.act_dim <= 8 && lay.val_dim <= 8, rows, st);
+        return launch_step_bf16(a, d, ws + pl.off_st, pl.tiles, dw_blocks, st);
     }
     if (f32_split()) {  // the default f32 path: three bf16 planes per operand on the bf16 matrix pipe (ppo_step_f32x.hip)
         if (s->tiles != nullptr) {
@@ -953,14 +934,12 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
         if (int rc = pack_tiles(s->params, lay, tiles, st)) return rc;
     }
     const size_t lds = Geo<4, 8>::LDS_BYTES;
-    const int v = dev_variant("RLX_STEP_VARIANT", 0);  // development: PD * 100 + ablation bits
     const bool op8 = lay.act_dim <= 8 && lay.val_dim <= 8;
 #define RLX_LAUNCH_FUSED(PDV, ABLV, OPV)                                                                                  \
     do {                                                                                                                  \
         if (int rc = set_lds(ppo_step_fused_kernel<4, 8, PDV, ABLV, OPV>, lds)) return rc;                                \
         hipLaunchKernelGGL((ppo_step_fused_kernel<4, 8, PDV, ABLV, OPV>), dim3(pl.tiles, 2), dim3(512), lds, st, a);      \
     } while (0)
-    // ablation builds (RLX_STEP_VARIANT, development): compiled only with -DRLX_DEV_VARIANTS, see tools/bench_step.py
     if (a.dec.on) {
         if (op8) {
             if (int rc = set_lds(ppo_step_fused_kernel<4, 8, 2, 0, 8, true>, lds)) return rc;
@@ -972,20 +951,7 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
     } else if (!op8) {
         RLX_LAUNCH_FUSED(2, 0, 16);
     } else {
-#ifdef RLX_DEV_VARIANTS
-        switch (v) {
-            case 201: RLX_LAUNCH_FUSED(2, 1, 8); break;
-            case 202: RLX_LAUNCH_FUSED(2, 2, 8); break;
-            case 204: RLX_LAUNCH_FUSED(2, 4, 8); break;
-            case 208: RLX_LAUNCH_FUSED(2, 8, 8); break;
-            case 400: RLX_LAUNCH_FUSED(4, 0, 8); break;
-            case 300: RLX_LAUNCH_FUSED(3, 0, 8); break;
-            default: RLX_LAUNCH_FUSED(2, 0, 8); break;
-        }
-#else
-        (void)v;
         RLX_LAUNCH_FUSED(2, 0, 8);
-#endif
     }
 #undef RLX_LAUNCH_FUSED
     RLX_LAUNCH_CHECK();

@@ -343,17 +343,6 @@ __global__ __launch_bounds__(512) void rollout_step_bf16_kernel(RolloutArgs a) {
     // lane's output element, and ALL three layers' weight fragments (16 rows per workgroup leave the registers for it:
     // 16 + 64 + 64 VGPRs).  The launch then costs one memory round trip plus the compute chain, instead of one round trip per
     // layer (each layer's first fragment loads used to be waited for by the previous epilogue's bias load).
-#ifdef RLX_DEV_VARIANTS
-    Stamps ts{a.stamps, 0};  // development: phase stamps of block 0 (tools/phase_times.py)
-#define RLX_MARK() ts.mark()
-#else
-#define RLX_MARK()
-#endif
-    RLX_MARK();
-#ifdef RLX_DEV_VARIANTS
-    if (a.stamps != nullptr) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // kernel arguments arrived
-#endif
-    RLX_MARK();
     StatesB<RT, NW> st;
     st.issue(states, D, m0, M);
     SmallInputsB<G::NT> si;
@@ -384,39 +373,28 @@ __global__ __launch_bounds__(512) void rollout_step_bf16_kernel(RolloutArgs a) {
     }
     gemm1.prefetch(tiles + Tiles::mat(y, 0), Tiles::K1P / 32);
     RLX_POINT(0)
-    RLX_MARK();  // every load issued
     st.commit(states, states_copy, D, m0, M, Xb);
-    RLX_MARK();  // states arrived
     si.commit(n_out, sBias, W4s, b4s, sStd);
     for (int i = n_out * W4S + tid; i < MAX_OUT * W4S; i += G::NT) W4s[i] = 0.f;
     RLX_POINT(1)
     lds_barrier();
-    RLX_MARK();  // inputs staged
     RLX_POINT(2)
     f32x4 acc[RT][G::CT];
     gemm1.run(Xb, acc);
     RLX_POINT(3)
-    RLX_MARK();
     epilogue_tanh_b<RT, NW, false>(acc, sBias, Xb, nullptr, nullptr, nullptr, 0, m0);
     RLX_POINT(4)
-    RLX_MARK();
     gemm2.run(Xb, acc);
     RLX_POINT(5)
 #undef RLX_POINT
-    RLX_MARK();
     epilogue_tanh_b<RT, NW, false>(acc, sBias + HID, Xb, nullptr, nullptr, nullptr, 0, m0);
-    RLX_MARK();
     gemm3.run(Xb, acc);
-    RLX_MARK();
     epilogue_tanh_b<RT, NW, false>(acc, sBias + 2 * HID, Xb, nullptr, nullptr, nullptr, 0, m0);
-    RLX_MARK();
 
     static_assert(G::BM * MAX_OUT <= G::NT, "one head output per lane");
     float* sP0 = b4s + MAX_OUT, *sP1 = sP0 + G::BM * MAX_OUT;
     head_forward_mfma<RT>(Xb, W4s, sP0, sP1);
     lds_barrier();
-    RLX_MARK();  // head
-#undef RLX_MARK
     if (tid < G::BM * n_out) {
         float s = fadd(sP0[orow * MAX_OUT + oo], sP1[orow * MAX_OUT + oo]);
         if (lay.off_b[y][3] >= 0) s = fadd(s, b4s[oo]);
@@ -470,7 +448,7 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
     // Workgroups go to the 8 XCDs round-robin (linear id % 8 = blockIdx.x % 8: gridDim.x is a multiple of 8 whenever the remap is
     // used).  The weight-gradient launch behind this one gives XCD x the split-K slabs over rows [x M / 8, (x + 1) M / 8); with the
     // identity map those rows were written by ALL XCDs and every operand fetch of that launch is a memory-side trip.  Remapped
-    // (development: RLX_FUSED_XCD_ROWS=1), XCD x writes exactly the rows it reads back next -- measured, same box, 3200 launches
+    // (StepArgs.xcd_rows = 1), XCD x writes exactly the rows it reads back next -- measured, same box, 3200 launches
     // each: weight-gradient launch 15.88 -> 15.64 us, this launch 25.16 -> 25.44 us (profiles/r03_xcd_row_map_*.txt).  A launch
     // boundary writes back AND invalidates the XCD's L2, so which XCD produced a line does not matter to the next launch; only
     // producer and consumer inside ONE launch could share an L2.  The identity map stays.
@@ -685,122 +663,6 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
 // fused optimizer-step kernel (2), bf16: weight gradients from the k-tiled transposed images, barrier-free.
 //   item = (slab, matrix, 128x128 tile); 4 waves as 2x2, each 4x4 tiles of 16x16 (v_mfma_f32_16x16x32_bf16, K = 32 batch rows)
 // ---------------------------------------------------------------------------------------------------------------
-#ifdef RLX_DEV_VARIANTS  // the register-streaming weight-gradient kernel of round 2 (RLX_DW_BF16_REG=1): kept for comparison only
-template <int PD>
-__global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_kernel(DwArgs a, const __bf16* __restrict__ st_tiles) {
-    __shared__ double s_red[NS * 4];
-    const rlx_mlp_layout& lay = a.lay;
-    const long long M = a.M;
-    const int tid = threadIdx.x;
-    const int gemm_blocks = round_up(a.gemm_items, 8);
-    int b = blockIdx.x;
-
-    if (b >= gemm_blocks) {
-        b -= gemm_blocks;
-        if (b < a.slabs * 2) {
-            head_reduce_block(a, b >> 1, b & 1, tid);
-        } else {
-            metric_block(a, s_red, tid, 256);
-        }
-        return;
-    }
-    const int item = (b & 7) * (gemm_blocks >> 3) + (b >> 3);
-    if (item >= a.gemm_items) return;
-    const int s = item / 20, w = item % 20;
-    int y, l, i0, j0;
-    if (w < 16) {
-        const int mat = w >> 2, tile = w & 3;
-        y = mat >> 1; l = 1 + (mat & 1); i0 = (tile >> 1) * 128; j0 = (tile & 1) * 128;
-    } else {
-        y = (w - 16) >> 1; l = 0; i0 = ((w - 16) & 1) * 128; j0 = 0;
-    }
-    const int nrb = (int)((M + 31) / 32);
-    const size_t mat_elems = (size_t)16 * nrb * 512;
-    const int Kin = l == 0 ? lay.obs_dim : HID;
-    const __bf16* A = reinterpret_cast<const __bf16*>(a.dz) + (size_t)(y * 3 + l) * mat_elems;
-    const __bf16* Bm = l == 0 ? st_tiles : reinterpret_cast<const __bf16*>(a.h) + (size_t)(y * 2 + l - 1) * mat_elems;
-    const int ncb_b = l == 0 ? 4 : 16;  // column blocks of the B image
-    const int lane = tid & 63, wave = tid >> 6, r16 = lane & 15, kq = lane >> 4;
-    const int wi = wave >> 1, wj = wave & 1;
-    if (j0 + wj * 64 >= Kin) return;  // first layers: only the first 64-column block holds inputs
-    const int rb0 = (int)((long long)s * a.rows_per_slab / 32);
-    const int rb1 = min(nrb, (int)(((long long)(s + 1) * a.rows_per_slab) / 32));
-    const int nkb = max(0, rb1 - rb0);
-
-    // fragment pointers: A tile (cb = (i0 + wi*64)/16 + ti, rb), B tile (cb = (j0 + wj*64)/16 + tj clamped, rb)
-    const __bf16* ap = A + ((size_t)((i0 + wi * 64) / 16) * nrb + rb0) * 512 + lane * 8;
-    int cbj[4];
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) cbj[tj] = min((j0 + wj * 64) / 16 + tj, ncb_b - 1);
-    const __bf16* bp = Bm + (size_t)rb0 * 512 + lane * 8;
-
-    struct Frag { bf16x8 a[4], b[4]; };
-    Frag ring[PD];
-    auto gload = [&](int kb, Frag& f) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f.a[t] = *reinterpret_cast<const bf16x8*>(ap + ((size_t)t * nrb + kb) * 512);
-            f.b[t] = *reinterpret_cast<const bf16x8*>(bp + ((size_t)cbj[t] * nrb + kb) * 512);
-        }
-    };
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int d = 0; d < PD; ++d)
-        if (d < nkb) gload(d, ring[d]);
-    __builtin_amdgcn_sched_barrier(0);
-    for (int kb0 = 0; kb0 < nkb; kb0 += PD) {
-#pragma unroll
-        for (int d = 0; d < PD; ++d) {
-            const int kb = kb0 + d;
-            if (kb < nkb) {
-#pragma unroll
-                for (int ti = 0; ti < 4; ++ti) {
-#pragma unroll
-                    for (int tj = 0; tj < 4; ++tj)
-                        acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[d].a[ti], ring[d].b[tj], acc[ti][tj], 0, 0, 0);
-                    float t8 = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) t8 += (float)ring[d].a[ti][e];
-                    bsum[ti] += t8;
-                }
-                if (kb + PD < nkb) gload(kb + PD, ring[d]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    float* slab = a.grads + (size_t)s * lay.n_params;
-    float* dW = slab + lay.off_w[y][l];
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) {
-            const int col = j0 + wj * 64 + tj * 16 + r16;
-            if (col < Kin) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = i0 + wi * 64 + ti * 16 + 4 * kq + r;
-                    dW[(size_t)row * Kin + col] = acc[ti][tj][r];
-                }
-            }
-        }
-    if (j0 == 0 && wj == 0) {  // bias gradient = column sums of dZ: lane (r16, kq) holds 8 of the 32 rows of column ti*16 + r16
-#pragma unroll
-        for (int ti = 0; ti < 4; ++ti) {
-            float tot = bsum[ti];
-            tot += __shfl_xor(tot, 16, 64);
-            tot += __shfl_xor(tot, 32, 64);
-            if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
-        }
-    }
-}
-
-#endif  // RLX_DEV_VARIANTS
-
 // ---------------------------------------------------------------------------------------------------------------
 // weight gradients, LDS-DMA variant: the 16 operand tiles of a k-block (8 of dZ^T, 8 of H^T, 1 KiB each, already in
 // lane-linear fragment order) are copied global -> LDS by `global_load_lds_dwordx4` (four 1 KiB DMAs per wave, no
@@ -898,7 +760,7 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
     long long* stp = (a.stamps != nullptr && item == 0 && tid == 0) ? a.stamps : nullptr;
     if (stp) stp[0] = clock64();
     constexpr int AHEAD = DW_NBUF - 1;  // k-blocks in flight
-    for (int rep = 0; rep < a.repeat; ++rep) {  // (1 pass; development: a second, L2-warm pass for timing)
+    for (int rep = 0; rep < a.repeat; ++rep) {  // (DwArgs.repeat is always 1)
     if (rep > 0) __builtin_amdgcn_s_barrier();  // everybody finished reading the last k-blocks before the ring is refilled
 #pragma unroll
     for (int d = 0; d < AHEAD; ++d)
@@ -1180,18 +1042,6 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
     }
 }
 
-template <typename K>
-int set_lds_b(K kern, size_t bytes) {
-    static thread_local const void* done[16] = {};
-    const void* key = reinterpret_cast<const void*>(kern);
-    for (const void* d : done)
-        if (d == key) return RLX_OK;
-    RLX_HIP_CHECK(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    for (auto& d : done)
-        if (d == nullptr) { d = key; break; }
-    return RLX_OK;
-}
-
 }  // namespace
 
 namespace step {
@@ -1203,33 +1053,11 @@ int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles,
 }
 
 int launch_rollout_bf16(const RolloutArgs& a, int blocks, hipStream_t st) {
-#ifdef RLX_DEV_VARIANTS
-    if (rollout_bm_bf16() == 32) {
-        const size_t lds = GeoB<2, 8>::LDS_BYTES;
-        if (int rc = set_lds_b(rollout_step_bf16_kernel<2>, lds)) return rc;
-        hipLaunchKernelGGL(rollout_step_bf16_kernel<2>, dim3(blocks), dim3(512), lds, st, a);
-    } else
-#endif
-    {
-        const size_t lds = GeoB<1, 8>::LDS_BYTES;
-        // Half layers requested one phase ahead of their use (ORDER 1345, see the kernel): measured in a replayed graph of 64 steps,
-        // 7.84 -> 6.84 us against everything up front (ORDER 0); profiles/r06_rollout_request_order.txt.
-#define RLX_RO(O) { if (int rc = set_lds_b(rollout_step_bf16_kernel<1, O>, lds)) return rc; hipLaunchKernelGGL((rollout_step_bf16_kernel<1, O>), dim3(blocks), dim3(512), lds, st, a); }
-#ifdef RLX_DEV_VARIANTS
-        switch (dev_variant("RLX_ROLLOUT_ORDER", 1345)) {
-            case 0: RLX_RO(0) break;
-            case 1135: RLX_RO(1135) break;
-            case 1134: RLX_RO(1134) break;
-            case 33: RLX_RO(33) break;
-            case 1355: RLX_RO(1355) break;
-            case 2345: RLX_RO(2345) break;
-            default: RLX_RO(1345) break;
-        }
-#else
-        RLX_RO(1345)
-#endif
-#undef RLX_RO
-    }
+    const size_t lds = GeoB<1, 8>::LDS_BYTES;
+    // Half layers requested one phase ahead of their use (ORDER 1345, see the kernel): measured in a replayed graph of 64 steps,
+    // 7.84 -> 6.84 us against everything up front (ORDER 0); profiles/r06_rollout_request_order.txt.
+    if (int rc = set_lds(rollout_step_bf16_kernel<1, 1345>, lds)) return rc;
+    hipLaunchKernelGGL((rollout_step_bf16_kernel<1, 1345>), dim3(blocks), dim3(512), lds, st, a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
@@ -1237,86 +1065,37 @@ int launch_rollout_bf16(const RolloutArgs& a, int blocks, hipStream_t st) {
 // workspace carve (bytes) of the bf16 step: tiled activation images instead of the f32 row-major ones
 size_t bf16_image_bytes(int64_t m) { return (size_t)16 * ((m + 31) / 32) * 512 * sizeof(__bf16); }
 
-int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, bool op8, bool rows, hipStream_t st) {
+int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st) {
     __bf16* stt = static_cast<__bf16*>(st_tiles);
 #define RLX_FUSED_LAUNCH(RTV, PDV, OPV, STV, DECV, LDSB)                                                                              \
     {                                                                                                                              \
         const size_t lb = (LDSB);                                                                                                  \
-        if (int rc = set_lds_b(ppo_step_fused_bf16_kernel<RTV, 8, PDV, OPV, STV, DECV>, lb)) return rc;                            \
+        if (int rc = set_lds(ppo_step_fused_bf16_kernel<RTV, 8, PDV, OPV, STV, DECV>, lb)) return rc;                            \
         hipLaunchKernelGGL((ppo_step_fused_bf16_kernel<RTV, 8, PDV, OPV, STV, DECV>), dim3(tiles, 2), dim3(512), lb, st, a, stt); \
     }
     const size_t lds32 = GeoB<2, 8>::LDS_BYTES;
-#ifdef RLX_DEV_VARIANTS
-    // development builds: the row-split launch, 64-row tiles (RLX_FUSED_RT=4), other weight-ring depths, phase stamps, LDS padding
-    const size_t lds64 = GeoB<4, 8>::LDS_BYTES + GeoB<4, 8>::KEEP_BYTES;
-    const int pd = dev_variant("RLX_FUSED_PD", 4);
-    if (rows) {  // `tiles` counts 64-row tiles
-        if (int rc = launch_fused_rows_bf16(a, st_tiles, tiles, st)) return rc;
-    } else if (fused_bm_bf16() == 64) {
-        if (a.dec.on) { if (op8) RLX_FUSED_LAUNCH(4, 4, 8, false, true, lds64) else RLX_FUSED_LAUNCH(4, 2, 16, false, true, lds64) }
-        else if (op8 && a.stamps != nullptr) RLX_FUSED_LAUNCH(4, 4, 8, true, false, lds64)
-        else if (op8 && pd == 8) RLX_FUSED_LAUNCH(4, 8, 8, false, false, lds64)
-        else if (op8) RLX_FUSED_LAUNCH(4, 4, 8, false, false, lds64)
-        else RLX_FUSED_LAUNCH(4, 2, 16, false, false, lds64)
-    } else if (a.dec.on) {
-        RLX_FUSED_LAUNCH(2, 4, 8, false, true, lds32)
-    } else if (a.stamps != nullptr) {
-        RLX_FUSED_LAUNCH(2, 4, 8, true, false, lds32)
-    } else if (pd == 2) {
-        RLX_FUSED_LAUNCH(2, 2, 8, false, false, lds32)
-    } else if (pd == 3) {
-        RLX_FUSED_LAUNCH(2, 3, 8, false, false, lds32)
-    } else {
-        RLX_FUSED_LAUNCH(2, 4, 8, false, false, lds32 + (size_t)dev_variant("RLX_FUSED_LDS_PAD", 0))
-    }
-#else
-    (void)rows;
-    (void)op8;
-    // the product launch: 32-row tiles (two workgroups per CU), weight ring of 4 stages; its decoupled-loss instantiation
+    // 32-row tiles (two workgroups per CU), weight ring of 4 stages; its decoupled-loss instantiation
     if (a.dec.on) RLX_FUSED_LAUNCH(2, 4, 8, false, true, lds32)
     else RLX_FUSED_LAUNCH(2, 4, 8, false, false, lds32)
-#endif
 #undef RLX_FUSED_LAUNCH
     RLX_LAUNCH_CHECK();
 #define RLX_DWR_LAUNCH(NB)                                                                                                         \
     {                                                                                                                              \
         const size_t rlds = (size_t)(NB) * DW_BUF_BYTES;                                                                           \
-        if (int rc = set_lds_b(ppo_step_dw_bf16_ring_kernel<NB>, rlds)) return rc;                                                 \
+        if (int rc = set_lds(ppo_step_dw_bf16_ring_kernel<NB>, rlds)) return rc;                                                 \
         hipLaunchKernelGGL(ppo_step_dw_bf16_ring_kernel<NB>, dim3(dw_blocks), dim3(DWR_THREADS), rlds, st, d, static_cast<const __bf16*>(stt)); \
     }
 #define RLX_DW_LAUNCH(NB)                                                                                                       \
     {                                                                                                                           \
         const size_t dlds = (size_t)(NB) * DW_BUF_BYTES;                                                                          \
-        if (int rc = set_lds_b(ppo_step_dw_bf16_lds_kernel<NB>, dlds)) return rc;                                               \
+        if (int rc = set_lds(ppo_step_dw_bf16_lds_kernel<NB>, dlds)) return rc;                                               \
         hipLaunchKernelGGL(ppo_step_dw_bf16_lds_kernel<NB>, dim3(dw_blocks), dim3(256), dlds, st, d, static_cast<const __bf16*>(stt)); \
     }
     // The ring kernel pays a longer prologue (the loaders' first hand-off) for its faster k-loop and store phase: it wins from
     // 4096 rows on (8192 rows, one box: 15.6 against 16.8 us, the slab reduce behind it 8.2 against 8.8), at 1024 rows the
     // previous kernel is ahead (9.4 against 10.5 us: profiles/r04_per_rank_share_*.txt).
-#ifdef RLX_DEV_VARIANTS
-    if (dev_variant("RLX_DW_BF16_REG", 0)) {  // the register-streaming variant (kept for comparison)
-        hipLaunchKernelGGL(ppo_step_dw_bf16_kernel<3>, dim3(dw_blocks), dim3(256), 0, st, d, static_cast<const __bf16*>(stt));
-    } else if (dev_variant("RLX_DW_RING", d.M >= 4096 ? 1 : 0) != 0) {
-        switch (dev_variant("RLX_DW_RING_NBUF", 4)) {
-            case 6: RLX_DWR_LAUNCH(6) break;
-            case 8: RLX_DWR_LAUNCH(8) break;
-            case 9: RLX_DWR_LAUNCH(9) break;
-            default: RLX_DWR_LAUNCH(4) break;
-        }
-    } else {
-        switch (dw_nbuf()) {
-            case 2: RLX_DW_LAUNCH(2) break;
-            case 4: RLX_DW_LAUNCH(4) break;
-            case 6: RLX_DW_LAUNCH(6) break;
-            case 9: RLX_DW_LAUNCH(9) break;
-            case 5: RLX_DW_LAUNCH(5) break;
-            default: RLX_DW_LAUNCH(3) break;
-        }
-    }
-#else
     if (d.M >= 4096) RLX_DWR_LAUNCH(4)
     else RLX_DW_LAUNCH(3)
-#endif
 #undef RLX_DWR_LAUNCH
 #undef RLX_DW_LAUNCH
     RLX_LAUNCH_CHECK();

@@ -1,5 +1,5 @@
-// ppo_step_bf16_parts.h -- device pieces shared by the bf16 fused launches (ppo_step_bf16.hip: column-split workgroups with the
-// weights streamed to registers; ppo_step_bf16_rows.hip: row-split waves with the weights staged through an LDS ring).
+// ppo_step_bf16_parts.h -- device pieces of the bf16 fused launch (ppo_step_bf16.hip: column-split workgroups with the weights
+// streamed to registers), shared with the f32x launches (ppo_step_f32x.hip).
 #pragma once
 
 #include "ppo_step_common.h"

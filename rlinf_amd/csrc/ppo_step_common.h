@@ -74,7 +74,7 @@ struct Stamps {
         ++n;
     }
 };
-// Ablation switches (development only: tools/bench_step.py times them; the product always runs ABL == 0)
+// Ablation switches of the exact-f32 fused kernel's ABL parameter (measurement only: the launches instantiate ABL == 0)
 constexpr int ABL_NO_TANH = 1, ABL_NO_FLUSH = 2, ABL_NO_WLOAD = 4, ABL_NO_MFMA = 8;
 
 // stage the head weight [n_out][256] (+ bias) into LDS with a padded row stride
@@ -198,7 +198,7 @@ struct StepArgs {
     long long M;
     rlx_ppo_loss_params p;
     float grad_out;             // d(total)/d(loss) of this micro-batch (1 / gradient_accumulation)
-    int merged_loss_pass;       // bf16 launch: element math + loss element + dOut in one pass where the shapes allow (development: RLX_FUSED_MERGED=0)
+    int merged_loss_pass;       // bf16 launch: element math + loss element + dOut in one pass where the shapes allow (always 1)
     int xcd_rows;               // bf16 launch: workgroup -> row-tile map that gives every XCD one CONTIGUOUS eighth of the rows (see the kernel)
     float* h;                   // [2 nets][2][M][256]  hidden activations 1, 2   (B operands of the weight gradients)
     float* dz;                  // [2 nets][3][M][256]  pre-activation gradients  (A operands)
@@ -223,8 +223,7 @@ struct DwArgs {
     int head_parts;          // head-gradient partial slots per network
     int head_stride;
     int gemm_items;          // slabs * 20, the grid holds round_up(gemm_items, 8) GEMM blocks
-    int repeat;              // 1; development (RLX_DW_REPEAT = 2, TIMING ONLY -- the sums come out doubled): the bf16 LDS-DMA kernel walks
-                             // its k-blocks twice, the second time with its operands warm in its XCD's L2
+    int repeat;              // always 1 (kept so that the argument offsets stay put): the bf16 LDS-DMA kernel walks its k-blocks `repeat` times
     float* grads;            // [slabs][n_params]
     rlx_ppo_loss_params p;
     int has_mask, has_msum;
@@ -353,19 +352,6 @@ int set_lds(K kern, size_t bytes) {
     return RLX_OK;
 }
 
-// Development switches.  The PRODUCT build reads no kernel-variant environment variable at all: every switch returns its default --
-// the measured-best path -- and the variant kernels behind the switches are not even compiled (the `#ifdef RLX_DEV_VARIANTS`
-// blocks of the .hip files).  A development build (RLX_CXXFLAGS=-DRLX_DEV_VARIANTS RLX_BUILD_TAG=dev python -m rlinf_amd.csrc.build,
-// loaded with RLX_LIB_TAG=dev) reads the variable at every call; rlx_dev_variants() tells a caller which build it loaded.
-#ifdef RLX_DEV_VARIANTS
-inline int dev_variant(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-#else
-inline int dev_variant(const char*, int dflt) { return dflt; }
-#endif
-
 inline int head_stride_of(const rlx_mlp_layout* lay) {
     const int n = std::max(lay->act_dim, lay->val_dim);
     return round_up(n * HID + 2 * n, 4);
@@ -374,36 +360,27 @@ inline int head_stride_of(const rlx_mlp_layout* lay) {
 struct StepPlan {
     int tiles;        // row tiles of the fused kernel (its grid)
     int loss_slots;   // metric partial slots per network (one per tile)
-    int head_parts;   // head-gradient partial slots per network (one per 32 rows; the row-split bf16 launch: one per 64-row tile)
+    int head_parts;   // head-gradient partial slots per network (one per 32 rows)
     int slabs, rows_per_slab, head_stride;
     size_t off_h, off_dz, off_head, off_loss, off_tiles, off_st, bytes;
 };
 constexpr int STEP_BM = 64;
-// rows per workgroup of the bf16 fused launch: 32 (default: two workgroups per CU at 8192 rows -- their phases, matrix pipe /
-// VALU epilogues / barrier and memory latency, overlap; 58 KB of LDS and 128 VGPRs each) or 64 (RLX_FUSED_RT=4: one per CU,
-// half the weight-fragment traffic, 157 KB of LDS).  Measured (profiles/r02_fused_rows_per_workgroup.txt): 25.6 against 27.7 us.
-// rows per workgroup of the bf16 rollout launch (every workgroup pulls its network's whole 0.29 MB tile image through the L2)
-inline int rollout_bm_bf16() { return dev_variant("RLX_ROLLOUT_RT", 1) == 2 ? 32 : 16; }
-inline int dw_nbuf() { return dev_variant("RLX_DW_NBUF", 3); }  // LDS ring depth of the bf16 weight-gradient launch (3, 4, 5, 6, 9)
-inline int fused_bm_bf16() { return dev_variant("RLX_FUSED_RT", 2) == 4 ? 64 : 32; }
-// The row-split bf16 launch (ppo_step_bf16_rows.hip: 64 rows per workgroup, one wave per 16 rows, weights through an LDS ring) for
-// the shapes it covers (fused_rows_eligible), behind RLX_FUSED_ROWS=1 while it is being tuned.
-inline bool fused_rows_bf16() { return dev_variant("RLX_FUSED_ROWS", 0) != 0; }
-bool fused_rows_eligible(const rlx_mlp_layout& lay, const rlx_ppo_loss_params& p);
 // precision "32": true (default) = the f32 launches run on the bf16 matrix pipe with three-plane operands (ppo_step_f32x.hip),
 // false (RLX_F32_EXACT_MFMA=1, read once per process) = the exact-f32-MFMA launches of ppo_step.hip.  The f32 weight image
 // (rlx_mlp_pack_tiles / the optimizer's tile refresh) follows the same switch.
 bool f32_split();
 size_t f32x_tiles_bytes();
+// rows per workgroup of the bf16 fused launch: 32 (two workgroups per CU at 8192 rows -- their phases, matrix pipe / VALU
+// epilogues / barrier and memory latency, overlap; 58 KB of LDS and 128 VGPRs each).  64 (one per CU, half the weight-fragment
+// traffic, 157 KB of LDS) measured 27.7 against 25.6 us and was removed (profiles/r02_fused_rows_per_workgroup.txt).
 // rows per workgroup of the f32x fused launch: 32 (the three-plane slab allows one workgroup per CU either way; 64 rows -- half the
-// weight bytes per row, ONE round of 256 workgroups at 8192 rows -- measured the same 82 us: development builds only, RLX_F32X_RT=4)
-inline int f32x_bm() { return dev_variant("RLX_F32X_RT", 2) == 4 ? 64 : 32; }
-inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = false, bool rows = false) {
+// weight bytes per row, ONE round of 256 workgroups at 8192 rows -- measured the same 82 us and was removed, profiles/r05_f32x_*)
+inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = false) {
     StepPlan pl{};
     const bool f32x = !bf16 && f32_split();
-    const int bm = (bf16 && rows) ? 64 : bf16 ? fused_bm_bf16() : f32x ? f32x_bm() : STEP_BM;
+    const int bm = bf16 || f32x ? 32 : STEP_BM;
     pl.tiles = ceil_div(m, bm);
-    pl.head_parts = (bf16 && rows) ? pl.tiles : pl.tiles * (bm / 32);
+    pl.head_parts = pl.tiles * (bm / 32);
     pl.loss_slots = pl.tiles;
     // 20 GEMM items per slab.  Every slab is 1.15 MB written here and read back by the slab reduce through the memory side:
     // (round 2, the LDS-DMA kernel with the copies in the compute waves: 16 slabs = 1.25 workgroups per CU was its best trade --
@@ -418,7 +395,6 @@ inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = fals
     // f32 through bf16 planes: the loader-wave ring at every size (144 KiB of LDS: one workgroup per CU) -> the same 10-slab plan
     int want = bf16 ? (m >= 4096 ? std::max(1, (num_cu() - 1) / 25) : 5 * num_cu() / (4 * 20))   // (below 4096 rows: the previous kernel and its plan)
                     : f32x ? std::max(1, (num_cu() - 1) / 25) : 2 * num_cu() / 20;
-    want = std::max(1, dev_variant("RLX_DW_SLABS", want));  // development: tools/bench_step.py sweeps it
     // ... and at least 256 rows (8 k-blocks) per slab: a data-parallel rank's small minibatch should not pay 16 slabs of traffic
     int slabs = std::max(1, std::min(want, ceil_div(m, 256)));
     pl.rows_per_slab = round_up(ceil_div(m, slabs), 32);
@@ -455,8 +431,7 @@ extern long long* g_timing_buffer;  // development: phase stamps (rlx_dev_set_ti
 // bf16 launches (ppo_step_bf16.hip)
 int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
 int launch_rollout_bf16(const RolloutArgs& a, int blocks, hipStream_t st);
-int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles64, int dw_blocks, bool op8, bool rows, hipStream_t st);
-int launch_fused_rows_bf16(const StepArgs& a, void* st_tiles, int tiles64, hipStream_t st);  // ppo_step_bf16_rows.hip
+int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles32, int dw_blocks, hipStream_t st);
 // f32 on the bf16 matrix pipe (ppo_step_f32x.hip)
 int pack_tiles_f32x(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
 int launch_rollout_f32x(const RolloutArgs& a, int blocks, hipStream_t st);

@@ -340,7 +340,7 @@ __device__ __forceinline__ void head_forward_mfma_x(const __bf16* Xb, const floa
 // ---------------------------------------------------------------------------------------------------------------
 // rollout step (RT = 1, NW = 8): the launch of rollout_step_bf16_kernel with three-plane operands
 // ---------------------------------------------------------------------------------------------------------------
-template <int PD>  // weight-ring depth (development: RLX_F32X_ROLLOUT_PD)
+template <int PD>  // weight-ring depth
 __global__ __launch_bounds__(512) void rollout_step_f32x_kernel(RolloutArgs a) {
     constexpr int RT = 1, NW = 8;
     touch_kernargs<(int)sizeof(RolloutArgs)>();
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(512) void rollout_step_f32x_kernel(RolloutArgs a) {
 // fused optimizer-step kernel (1), f32 through bf16 planes.  Images (plane-major inside every matrix, nrb = ceil(M / 32)):
 //   h  : [2 nets][2][3 planes][16 cb][nrb] tiles    dz : [2 nets][3][3 planes][16 cb][nrb] tiles    st : [3 planes][4 cb][nrb] tiles
 // ---------------------------------------------------------------------------------------------------------------
-template <int RT, int NW, int PD, bool DEC, bool STAMPS = false>  // STAMPS: development build with phase stamps (tools/phase_times.py)
+template <int RT, int NW, int PD, bool DEC, bool STAMPS = false>  // STAMPS: phase stamps (tools/phase_times.py); the launch instantiates false
 __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArgs a, __bf16* st_tiles) {
     typedef GeoX<RT, NW> G;
     constexpr int BM = G::BM, CT = G::CT;
@@ -833,18 +833,6 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
     }
 }
 
-template <typename K>
-int set_lds_x(K kern, size_t bytes) {
-    static thread_local const void* done[8] = {};
-    const void* key = reinterpret_cast<const void*>(kern);
-    for (const void* d : done)
-        if (d == key) return RLX_OK;
-    RLX_HIP_CHECK(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    for (auto& d : done)
-        if (d == nullptr) { d = key; break; }
-    return RLX_OK;
-}
-
 }  // namespace
 
 namespace step {
@@ -864,21 +852,7 @@ int pack_tiles_f32x(const float* params, const rlx_mlp_layout& lay, void* tiles,
 
 int launch_rollout_f32x(const RolloutArgs& a, int blocks, hipStream_t st) {
     const size_t lds = GeoX<1, 8>::LDS_BYTES;
-#ifdef RLX_DEV_VARIANTS
-    if (dev_variant("RLX_F32X_ROLLOUT_PD", 2) == 4) {
-        if (int rc = set_lds_x(rollout_step_f32x_kernel<4>, lds)) return rc;
-        hipLaunchKernelGGL(rollout_step_f32x_kernel<4>, dim3(blocks), dim3(512), lds, st, a);
-        RLX_LAUNCH_CHECK();
-        return RLX_OK;
-    }
-    if (dev_variant("RLX_F32X_ROLLOUT_PD", 2) == 8) {
-        if (int rc = set_lds_x(rollout_step_f32x_kernel<8>, lds)) return rc;
-        hipLaunchKernelGGL(rollout_step_f32x_kernel<8>, dim3(blocks), dim3(512), lds, st, a);
-        RLX_LAUNCH_CHECK();
-        return RLX_OK;
-    }
-#endif
-    if (int rc = set_lds_x(rollout_step_f32x_kernel<2>, lds)) return rc;
+    if (int rc = set_lds(rollout_step_f32x_kernel<2>, lds)) return rc;
     hipLaunchKernelGGL(rollout_step_f32x_kernel<2>, dim3(blocks), dim3(512), lds, st, a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
@@ -889,29 +863,18 @@ int launch_step_f32x(const StepArgs& a, const DwArgs& d, void* st_tiles, int til
 #define RLX_F32X_LAUNCH(RTV, PDV, DECV, STV)                                                                                       \
     {                                                                                                                              \
         const size_t lds = GeoX<RTV, 8>::LDS_BYTES;                                                                                \
-        if (int rc = set_lds_x(ppo_step_fused_f32x_kernel<RTV, 8, PDV, DECV, STV>, lds)) return rc;                                \
+        if (int rc = set_lds(ppo_step_fused_f32x_kernel<RTV, 8, PDV, DECV, STV>, lds)) return rc;                                \
         hipLaunchKernelGGL((ppo_step_fused_f32x_kernel<RTV, 8, PDV, DECV, STV>), dim3(tiles, 2), dim3(512), lds, st, a, stt);     \
     }
-    // `tiles` counts f32x_bm()-row tiles (plan_step).  Measured on one box (profiles/r05_f32x_*): 64-row tiles (half the weight bytes
+    // `tiles` counts 32-row tiles (plan_step).  Measured on one box (profiles/r05_f32x_*): 64-row tiles (half the weight bytes
     // per row, one round of workgroups) 82.2 us against 82.7 us for 32-row tiles; weight-ring depth 1 / 2 / 3: 79.7 / 79.9 / 81.2 us
-    // -- the launch is bound by neither.  32 rows, depth 2 it is; the rest is compiled with -DRLX_DEV_VARIANTS only.
-#ifdef RLX_DEV_VARIANTS
-    if (a.stamps != nullptr && !a.dec.on) {  // phase stamps (tools/phase_times.py)
-        if (f32x_bm() == 64) RLX_F32X_LAUNCH(4, 1, false, true)
-        else RLX_F32X_LAUNCH(2, 2, false, true)
-    } else if (f32x_bm() == 64) {
-        if (a.dec.on) RLX_F32X_LAUNCH(4, 1, true, false)
-        else RLX_F32X_LAUNCH(4, 1, false, false)
-    } else
-#endif
-    {
-        if (a.dec.on) RLX_F32X_LAUNCH(2, 2, true, false)
-        else RLX_F32X_LAUNCH(2, 2, false, false)
-    }
+    // -- the launch is bound by neither.  32 rows, depth 2 it is; the other forms were removed.
+    if (a.dec.on) RLX_F32X_LAUNCH(2, 2, true, false)
+    else RLX_F32X_LAUNCH(2, 2, false, false)
 #undef RLX_F32X_LAUNCH
     RLX_LAUNCH_CHECK();
     const size_t rlds = (size_t)DWX_NBUF * DWX_BUF_BYTES;
-    if (int rc = set_lds_x(ppo_step_dw_f32x_kernel, rlds)) return rc;
+    if (int rc = set_lds(ppo_step_dw_f32x_kernel, rlds)) return rc;
     hipLaunchKernelGGL(ppo_step_dw_f32x_kernel, dim3(dw_blocks), dim3(DWX_THREADS), rlds, st, d, static_cast<const __bf16*>(stt));
     RLX_LAUNCH_CHECK();
     return RLX_OK;

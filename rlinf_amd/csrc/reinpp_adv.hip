@@ -22,10 +22,6 @@
 
 #include "rlx_common.h"
 
-#ifndef RLX_REINPP_NT
-#define RLX_REINPP_NT 1  // streaming loads of logprob / ref_logprob, streaming store of the normalised output (+6 %, measured)
-#endif
-
 namespace rlx {
 namespace {
 
@@ -85,14 +81,9 @@ __global__ __launch_bounds__(RTV) void reinpp_returns_kernel(const float* __rest
         Tile t;
         const long long q = tile * TILE + (long long)tid * 4;
         const long long qc = (vec_ok && q + 4 <= S) ? q : 0;  // clamped, unconditional loads (partial tiles take the scalar path)
-        if (has_kl && vec_ok) {
-#if RLX_REINPP_NT
+        if (has_kl && vec_ok) {  // streaming loads here and in the register kernel, a streaming store of the output: +6 %, measured
             t.a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(lp + qc));
             t.c = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(rf + qc));
-#else
-            t.a = *reinterpret_cast<const f32x4*>(lp + qc);
-            t.c = *reinterpret_cast<const f32x4*>(rf + qc);
-#endif
         } else {
             t.a = f32x4{0.f, 0.f, 0.f, 0.f};
             t.c = t.a;
@@ -259,13 +250,8 @@ __global__ __launch_bounds__(64 * (S < 4 ? 4 : S)) void reinpp_returns_reg_kerne
     for (int u = 0; u < U; ++u) {  // (clamped, unconditional: all in flight together)
         const int q = min(max(nq - 64 * (k0 + u + 1) + lane, 0), nq - 1);
         if (has_kl) {
-#if RLX_REINPP_NT
             a[u] = __builtin_nontemporal_load(lp4 + q);
             c[u] = __builtin_nontemporal_load(rf4 + q);
-#else
-            a[u] = lp4[q];
-            c[u] = rf4[q];
-#endif
         } else {
             a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
             c[u] = a[u];
@@ -429,13 +415,9 @@ __global__ __launch_bounds__(RT) void reinpp_normalize_kernel(float* __restrict_
         float4 v = x4[i];
         v.x = fmul(fsub(v.x, mean), rstd), v.y = fmul(fsub(v.y, mean), rstd);
         v.z = fmul(fsub(v.z, mean), rstd), v.w = fmul(fsub(v.w, mean), rstd);
-#if RLX_REINPP_NT
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         const f32x4 o = {v.x, v.y, v.z, v.w};
         __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(x) + i);
-#else
-        x4[i] = v;
-#endif
     }
     for (long long i = n4 * 4 + (long long)blockIdx.x * RT + threadIdx.x; i < n; i += stride) x[i] = fmul(fsub(x[i], mean), rstd);
 }
@@ -481,17 +463,10 @@ extern "C" int rlx_reinpp_seq_adv(const float* rewards, const uint8_t* loss_mask
         // lanes per sequence (a tile is 4 x lanes tokens), measured on three shapes (profiles/r02_reinpp_lanes_sweep.txt):
         // rows of <= 2048 tokens want 64 lanes (0.65-0.66 of the HBM peak against 0.58-0.62 with 256: a row is 4-8 short tiles
         // of one wave each, no cross-wave hand-off, and many rows share a CU), rows of >= 4096 tokens 256 lanes (0.69 against 0.63)
-#ifdef RLX_DEV_VARIANTS
-        static const int forced = getenv("RLX_REINPP_RT") ? atoi(getenv("RLX_REINPP_RT")) : 0;  // development override
-#else
-        constexpr int forced = 0;
-#endif
-        const int rtv = forced ? forced : (seq <= 2048 ? 64 : (seq < 4096 ? 128 : 256));
+        const int rtv = seq <= 2048 ? 64 : (seq < 4096 ? 128 : 256);
         if (rtv == 64) hipLaunchKernelGGL(reinpp_returns_kernel<64>, dim3((unsigned)bsz), dim3(64), 0, st, rewards, loss_mask, logprob, ref_logprob, kl_type,
                        kl_beta, advantages, partials, (long long)bsz, (long long)seq, (int)((bits & 15) == 0));
         else if (rtv == 128) hipLaunchKernelGGL(reinpp_returns_kernel<128>, dim3((unsigned)bsz), dim3(128), 0, st, rewards, loss_mask, logprob, ref_logprob, kl_type,
-                       kl_beta, advantages, partials, (long long)bsz, (long long)seq, (int)((bits & 15) == 0));
-        else if (rtv == 512) hipLaunchKernelGGL(reinpp_returns_kernel<512>, dim3((unsigned)bsz), dim3(512), 0, st, rewards, loss_mask, logprob, ref_logprob, kl_type,
                        kl_beta, advantages, partials, (long long)bsz, (long long)seq, (int)((bits & 15) == 0));
         else hipLaunchKernelGGL(reinpp_returns_kernel<256>, dim3((unsigned)bsz), dim3(256), 0, st, rewards, loss_mask, logprob, ref_logprob, kl_type,
                        kl_beta, advantages, partials, (long long)bsz, (long long)seq, (int)((bits & 15) == 0));
