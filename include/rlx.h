@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 115 /* 0.1.5: bumped whenever an argument struct or a signature changes (0.1.5: the development-build query removed;
+#define RLX_VERSION 116 /* 0.1.6: bumped whenever an argument struct or a signature changes (0.1.6: rlx_grpo_video_adv, rlx_raw_adv,
+                           * rlx_raw_adv_workspace_bytes; 0.1.5: the development-build query removed;
                            * 0.1.4: rlx_grpo_dynamic_adv, rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries
                            * rlx_opd_*; round 6: rlx_xgmi_self_timing, the
                            * exchange inside rlx_xgmi_clip_adamw_step under sync_words; round 5: rlx_categorical_sample's
@@ -730,6 +731,41 @@ int rlx_loss_scale_rows(void* x, int dtype, const float* row_factor, float facto
                         rlx_stream_t stream);
 int rlx_loss_scale_turn(void* loss_scales, int dtype, const uint8_t* response_mask, const int32_t* plan, int64_t num_seq,
                         int64_t num_groups, int64_t seq, int32_t* zero_flag, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a13b  grpo_video_adv  <- adv_type "grpo_video" (embodied only): compute_grpo_video_advantages
+ *                          rlinf/algorithms/advantages.py:124-164 behind preprocess / postprocess_embodied_advantages
+ *                          rlinf/algorithms/utils.py:67-131,155-174; the dispatcher runs NO score scan for it (registry.py:110)
+ *   rewards [n_chunk, B, C] f32, loss_mask [n_chunk, B, C] u8 -> advantages [n_chunk, B, C] f32; element (n, b, c) is step
+ *   t = n * C + c of env b, envs are B / group_size prompts of group_size consecutive envs; dones play no part.
+ *   mode RLX_GRPO_VIDEO_FRAME: mean / unbiased std over the group_size rewards of every (t, prompt);
+ *   RLX_GRPO_VIDEO_VIDEO: over all T * group_size rewards of a prompt, T = n_chunk * C (summed in the order t * G + g, so the
+ *   flattened [T, B, 1] view of a buffer gives the same bits).
+ *   adv = (r - mean) / (std + eps) * mask: moments, subtraction and division in f64, rounded to f32 once, then multiplied by
+ *   the mask (NaN stays NaN, a negative value gives -0.0 where masked).  A single value (group_size == 1 in frame mode,
+ *   T * group_size == 1 in video mode) has std NaN: NaN everywhere.  One launch, no workspace, fixed summation order: repeated
+ *   launches give the same bits.  Any group_size >= 1 dividing B, any C >= 1.
+ * ------------------------------------------------------------------------------------------ */
+enum rlx_grpo_video_mode { RLX_GRPO_VIDEO_FRAME = 0, RLX_GRPO_VIDEO_VIDEO = 1 };
+int rlx_grpo_video_adv(const float* rewards, const uint8_t* loss_mask, float* advantages, int n_chunk, int batch, int chunk,
+                       int group_size, int mode, float eps, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a13c  raw_adv  <- adv_type "raw": compute_raw_advantages rlinf/algorithms/advantages.py:410-438; embodied behind
+ *                   calculate_scores (rlx_episode_scores gives `scores`), reasoning behind
+ *                   preprocess_reasoning_advantages_inputs rlinf/algorithms/utils.py:220
+ *   scores [batch] f32, loss_mask [outer, batch, inner] u8 -> advantages [outer, batch, inner] f32; embodied
+ *   (n_chunk, B, C), reasoning (1, bsz, seq).  adv = scores[b] * mask (exact; -0.0 / NaN as the product gives them).
+ *   normalize != 0: valid = adv[mask]; when it is not empty, EVERY element becomes (adv - mean(valid)) / (std(valid) + eps),
+ *   unbiased std, so masked positions hold -mean / (std + eps); one valid element: NaN everywhere; none: the product stays.
+ *   The moments come from integer mask counts per env: count = sum cnt[b], and the sums of cnt[b] * d and cnt[b] * d^2 with
+ *   d = scores[b] - scores[0], f64, envs in index order -- independent of outer / inner, so a [T, B, 1] view of an
+ *   [n_chunk, B, C] mask gives the same bits.  normalize == 0: one launch, workspace unused (NULL accepted).
+ *   normalize != 0: two launches, workspace >= rlx_raw_adv_workspace_bytes, 8-byte aligned, not read before it is written.
+ * ------------------------------------------------------------------------------------------ */
+size_t rlx_raw_adv_workspace_bytes(int64_t outer, int64_t batch, int64_t inner);
+int rlx_raw_adv(const float* scores, const uint8_t* loss_mask, float* advantages, int64_t outer, int64_t batch, int64_t inner,
+                int normalize, float eps, void* workspace, size_t workspace_bytes, rlx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * t5  gae_seq  <- adv_type "gae" on reasoning batches: preprocess_reasoning_advantages_inputs rlinf/algorithms/utils.py:177-262

@@ -144,6 +144,7 @@ TOK_OUT_NAMES = {"loss": 0, "actor/policy_loss": 1, "actor/policy_loss_abs": 2, 
                  "actor/clipped_ratio": 5, "actor/dual_cliped_ratio": 6, "actor/approx_kl": 7, "actor/clip_fraction": 8,
                  "actor/entropy_loss": 9, "actor/kl_loss": 10, "actor/token_num": 11, "policy_on": 12}
 GRPO_DYN_MODES = {"trajectory": 0, "turn": 1}  # include/rlx.h: rlx_grpo_dyn_mode
+GRPO_VIDEO_MODES = {"frame": 0, "video": 1}  # include/rlx.h: rlx_grpo_video_mode
 OPD_OUT_FLOATS = 8  # include/rlx.h: rlx_opd_out
 OPD_OUT_NAMES = {"loss": 0, "actor/policy_loss": 1, "actor/opd_reward": 2, "actor/opd_reverse_kl": 3, "grad_div": 4,
                  "mask_count": 5}
@@ -257,6 +258,9 @@ PROTOTYPES = {
                                      c_float, c_void_p]),
     "rlx_loss_scale_rows": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int64, c_int64, c_void_p]),
     "rlx_loss_scale_turn": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "rlx_grpo_video_adv": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "rlx_raw_adv_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "rlx_raw_adv": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     "rlx_xgmi_create": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_void_p), c_void_p]),
     "rlx_xgmi_connect": (c_int, [c_void_p, c_void_p]),
     "rlx_xgmi_connect_local": (c_int, [POINTER(c_void_p), c_int]),
@@ -295,7 +299,7 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 115:
+    if lib.rlx_version() < 116:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents

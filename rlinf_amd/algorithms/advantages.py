@@ -1,6 +1,6 @@
-"""Built-in advantage estimators behind the registry names "gae", "grpo", "grpo_dynamic", "reinpp" and "opd"
-(mirror of rlinf/algorithms/advantages.py:24-121,167-407), served by gae_scan.hip / grpo_adv.hip / grpo_dynamic.hip /
-reinpp_adv.hip / opd.hip.
+"""Built-in advantage estimators behind all seven registry names of the reference -- "gae", "grpo", "grpo_video",
+"grpo_dynamic", "reinpp", "opd" and "raw" (mirror of rlinf/algorithms/advantages.py:24-438), served by gae_scan.hip /
+grpo_adv.hip / adv_video_raw.hip / grpo_dynamic.hip / reinpp_adv.hip / opd.hip.
 
 Two entry shapes exist for each name:
   * the reference's callee contract -- flattened ``[T, B]`` tensors, ``fn(**kwargs) -> (advantages,
@@ -231,9 +231,81 @@ def _native_grpo_dynamic_reasoning(*, rewards, loss_mask, group_size, idx_to_tra
     return _u.unstage(adv, loss_mask), None
 
 
+def _grpo_video_mode(kwargs: dict) -> str:
+    """advantages.py:153-162: anything but "frame" / "video" (None and a missing key included) is refused, before any launch."""
+    mode = kwargs.get("advantage_mode")
+    if mode not in ("frame", "video"):
+        raise ValueError(f"Unsupported grpo_video advantage_mode: {mode}")
+    return mode
+
+
+@register_advantage("grpo_video")
+def compute_grpo_video_advantages(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: int, **kwargs):
+    """Frame / chunk-level GRPO for video rewards (advantages.py:124-164), the reference's callee contract: rewards [T, B],
+    envs ordered as B / group_size prompts of group_size samples, loss_mask [T, B] -> (advantages [T, B], None).
+    advantage_mode "frame": mean / unbiased std over the group_size samples of every (step, prompt); "video": over all
+    T * group_size rewards of a prompt.  One launch of adv_video_raw.hip on the [T, B, 1] view."""
+    mode = _grpo_video_mode(kwargs)
+    dev = _u.compute_device(rewards, loss_mask)
+    adv = ops.grpo_video_adv(_tb(rewards.float(), dev), _tb(loss_mask, dev), int(group_size), mode)
+    return _u.unstage(adv[..., 0], rewards), None
+
+
+@register_advantage("raw")
+def compute_raw_advantages(rewards: torch.Tensor, loss_mask: torch.Tensor, normalize_advantages: bool = False, **kwargs):
+    """Raw (optionally standardized) scores as advantages (advantages.py:410-438), the reference's callee contract: rewards =
+    per-env scores ([B] or [num_groups, group_size]), loss_mask [T, B] -> (advantages [T, B], None).  adv = score[b] * mask;
+    with normalize_advantages every element is standardized by the moments of the valid ones (safe_normalize's rule: one valid
+    element gives NaN, none leaves the product).  adv_video_raw.hip on the [T, B, 1] view."""
+    dev = _u.compute_device(rewards, loss_mask)
+    scores = _u.stage(rewards, dev).float().reshape(-1)
+    adv = ops.raw_adv(scores, _tb(loss_mask, dev), bool(normalize_advantages))
+    return _u.unstage(adv[..., 0], loss_mask), None
+
+
+def _native_grpo_video(*, rewards, dones=None, loss_mask=None, group_size=8, reward_type="action_level", **kwargs):
+    """grpo_video on the [n_chunk, B, C] buffers: no score scan (registry.py:110), dones unused."""
+    mode = _grpo_video_mode(kwargs)
+    if loss_mask is None:
+        raise TypeError("compute_grpo_video_advantages() missing required argument: 'loss_mask'")
+    dev = _u.compute_device(rewards, loss_mask)
+    r, m = _u.stage(rewards, dev), _u.stage(loss_mask, dev)
+    if reward_type == "chunk_level":
+        r, m = r.sum(dim=-1, keepdim=True), m.max(dim=-1, keepdim=True)[0]
+    adv = ops.grpo_video_adv(r.float(), m, int(group_size), mode)
+    return {"advantages": _u.unstage(adv, rewards)}
+
+
+def _native_raw(*, rewards, dones, loss_mask=None, reward_type="action_level", normalize_advantages=False, **kwargs):
+    """raw on the [n_chunk, B, C] buffers: the existing score scan (rlx_episode_scores), then score[b] * mask."""
+    if loss_mask is None:
+        raise TypeError("compute_raw_advantages() missing required argument: 'loss_mask'")
+    dev = _u.compute_device(rewards, dones, loss_mask)
+    r, d, m = _u.stage(rewards, dev), _u.stage(dones, dev), _u.stage(loss_mask, dev)
+    if reward_type == "chunk_level":
+        r, d, m, _ = _chunk_level(r, d, m, None)
+    adv = ops.raw_adv(ops.episode_scores(r.float(), d), m, bool(normalize_advantages))
+    return {"advantages": _u.unstage(adv, rewards)}
+
+
+def _native_raw_reasoning(*, rewards, loss_mask, normalize_advantages=False, **kwargs):
+    """Reasoning raw: rewards [bsz], loss_mask [bsz, seq] -> (advantages [bsz, seq] contiguous, None); replaces
+    preprocess_reasoning_advantages_inputs + compute_raw_advantages + postprocess (utils.py:177-277) without a transpose."""
+    if rewards.ndim != 1:
+        raise AssertionError(f"Unsupported reward shape {rewards.shape}")
+    if loss_mask.dim() != 2:
+        return None  # the generic route fails the way the reference does
+    dev = _u.compute_device(rewards, loss_mask)
+    adv = ops.raw_adv(_u.stage(rewards, dev).float(), _u.stage(loss_mask, dev), bool(normalize_advantages))
+    return _u.unstage(adv, loss_mask), None
+
+
 _mark_native_adv("gae", _native_gae)
 _mark_native_adv("grpo", _native_grpo)
 _mark_native_adv("gae", _native_gae_reasoning, task_type="reasoning")
 _mark_native_adv("grpo", _native_grpo_reasoning, task_type="reasoning")
 _mark_native_adv("reinpp", _native_reinpp_reasoning, task_type="reasoning")
 _mark_native_adv("grpo_dynamic", _native_grpo_dynamic_reasoning, task_type="reasoning")
+_mark_native_adv("grpo_video", _native_grpo_video)  # embodied only: a reasoning batch fails in the generic route, as upstream
+_mark_native_adv("raw", _native_raw)
+_mark_native_adv("raw", _native_raw_reasoning, task_type="reasoning")

@@ -13,6 +13,8 @@ every metric after it, the callees registered here take the already-shaped tenso
 == 1 per element) and return plain tensors, exactly what that caller expects.  The on-policy distillation names ("opd", advantage
 and loss) are replaced only in an RLinf that registers them itself, i.e. one whose dispatcher has the OPD arm.  "grpo_dynamic" is
 likewise replaced only where RLinf registers it; the loss scales ("group_level", "agent_level", "turn_level") only in an RLinf that has register_loss_scale.
+"grpo_video" and "raw" follow the same rule: each is replaced only in an RLinf whose ADV_REGISTRY already holds it, because its dispatcher
+then skips the score scan for "grpo_video" and its reasoning pre-processing has the "raw" arm.
 """
 
 from __future__ import annotations
@@ -42,6 +44,11 @@ def register() -> None:
     # reasoning pre-processing then has the grpo_dynamic arm (utils.py:207-215) that shapes the callee's inputs
     if "grpo_dynamic" in getattr(ref_registry, "ADV_REGISTRY", {}):
         ref_registry.register_advantage("grpo_dynamic")(adv.compute_grpo_dynamic_advantages)
+    # "grpo_video" (the dispatcher's no-score-scan arm, registry.py:110) and "raw" (the reasoning arm, utils.py:220) likewise
+    if "grpo_video" in getattr(ref_registry, "ADV_REGISTRY", {}):
+        ref_registry.register_advantage("grpo_video")(adv.compute_grpo_video_advantages)
+    if "raw" in getattr(ref_registry, "ADV_REGISTRY", {}):
+        ref_registry.register_advantage("raw")(adv.compute_raw_advantages)
     # the loss-scale processes only where this RLinf has their registry (registry.py:128-147)
     if hasattr(ref_registry, "register_loss_scale"):
         from rlinf_amd.algorithms import loss_scales as ls

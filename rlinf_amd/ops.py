@@ -306,6 +306,51 @@ def episode_scores(rewards: torch.Tensor, dones: torch.Tensor) -> torch.Tensor:
     return scores
 
 
+def grpo_video_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: int, mode: str, eps: float = 1e-6) -> torch.Tensor:
+    """rewards [n,B,C] f32, loss_mask [n,B,C] bool -> advantages [n,B,C] f32 (advantages.py:124-164): per (step, prompt)
+    moments for mode "frame", per prompt for "video".  a13b."""
+    if mode not in _lib.GRPO_VIDEO_MODES:
+        raise ValueError(f"Unsupported grpo_video advantage_mode: {mode}")
+    lib = _lib.load()
+    dev = _dev(rewards, loss_mask)
+    n, B, C = _nbc(rewards, "rewards")
+    r = _as_f32(rewards, "rewards")
+    m8 = _as_u8(loss_mask)
+    if tuple(m8.shape) != (n, B, C):
+        raise RlxError(f"loss_mask must be {(n, B, C)}, got {tuple(m8.shape)}")
+    if group_size < 1 or B % group_size != 0:
+        raise RlxError(f"batch {B} not divisible by group_size {group_size}")
+    adv = torch.empty_like(r)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rlx_grpo_video_adv(r.data_ptr(), m8.data_ptr(), adv.data_ptr(), n, B, C, int(group_size),
+                                          _lib.GRPO_VIDEO_MODES[mode], float(eps), _stream_ptr(dev)), "rlx_grpo_video_adv")
+    return adv
+
+
+def raw_adv(scores: torch.Tensor, loss_mask: torch.Tensor, normalize: bool = False, eps: float = 1e-5) -> torch.Tensor:
+    """scores [B] f32 (any shape with B elements), loss_mask [n,B,C] or [bsz,seq] bool -> scores[b] * mask in the mask's shape,
+    f32; ``normalize`` standardizes EVERY element with the moments of the valid ones (advantages.py:410-438).  a13c."""
+    lib = _lib.load()
+    dev = _dev(scores, loss_mask)
+    if loss_mask.dim() == 3:
+        outer, batch, inner = loss_mask.shape
+    elif loss_mask.dim() == 2:
+        outer, (batch, inner) = 1, loss_mask.shape
+    else:
+        raise RlxError(f"loss_mask must be [n_chunk, batch, chunk] or [bsz, seq]; got {tuple(loss_mask.shape)}")
+    sc = _as_f32(scores.reshape(-1), "scores")
+    if sc.numel() != batch:
+        raise RlxError(f"scores must have {batch} elements, got {sc.numel()}")
+    m8 = _as_u8(loss_mask)
+    adv = torch.empty(tuple(loss_mask.shape), dtype=torch.float32, device=dev)
+    ws_bytes = lib.rlx_raw_adv_workspace_bytes(outer, batch, inner) if normalize else 0
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if normalize else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.rlx_raw_adv(sc.data_ptr(), m8.data_ptr(), adv.data_ptr(), outer, batch, inner, int(bool(normalize)),
+                                   float(eps), _ptr(ws), ws_bytes, _stream_ptr(dev)), "rlx_raw_adv")
+    return adv
+
+
 # --------------------------------------------------------------------------------------------
 # a18-a21  fused PPO loss (forward + backward) as an autograd node
 # --------------------------------------------------------------------------------------------

@@ -303,7 +303,7 @@ class EmbodiedFSDPActor(Worker):
                 task_type=self.cfg.runner.task_type, adv_type=alg.adv_type, rewards=b["rewards"], dones=b["dones"],
                 values=b.get("prev_values"), gamma=alg.get("gamma", 1), gae_lambda=alg.get("gae_lambda", 1),
                 group_size=alg.get("group_size", 8), reward_type=alg.reward_type, loss_mask=b.get("loss_mask"),
-                loss_mask_sum=b.get("loss_mask_sum"),
+                loss_mask_sum=b.get("loss_mask_sum"), advantage_mode=alg.get("advantage_mode", None),
                 **({"normalize_advantages": False} if self.use_training_pipeline else {}))
             if self.use_training_pipeline and alg.get("normalize_advantages", True):
                 adv = out["advantages"].contiguous()
