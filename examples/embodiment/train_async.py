@@ -5,9 +5,11 @@ follows ``algorithm.loss_type``.  Of the reference's asynchronous learners the d
 
     python examples/embodiment/train_async.py --config-name maniskill_async_ppo_mlp [runner.max_epochs=20 ...]
 
-Rollout and learner share the resident trajectory buffer of one process here, so an iteration is rollout -> advantages ->
-run_training like the synchronous runner; what is asynchronous PPO about it is the data: every trajectory carries the
-policy version it was sampled with and the loss corrects for the distance to the version being trained.
+Rollout and learner share one process here.  Without the rollout-store keys an iteration is rollout -> advantages ->
+run_training like the synchronous runner, every trajectory stamped with the version being trained.  With
+``algorithm.rollout_store_size_per_rank`` / ``staleness_threshold`` (and e.g. ``runner.weight_sync_interval=2``) the rollout
+worker keeps sampling with the weights it last received, trajectories go through the learner's staleness-aware store, and a
+round trains on a batch of mixed policy versions; the staleness metrics are printed with the rest.
 """
 import argparse
 import json
@@ -57,8 +59,9 @@ def main():
             keep = ("rollout/rewards", "train/actor/total_loss", "train/actor/proximal_approx_kl", "train/actor/behav_approx_kl",
                     "train/actor/average_version", "train/critic/value_loss", "train/actor/grad_norm", "perf/env_steps_per_sec",
                     "time/step")
-            print(json.dumps({"step": step, **{k: (round(v, 6) if isinstance(v, float) else v) for k, v in m.items() if k in keep}}),
-                  flush=True)
+            stale = {k: v for k, v in m.items() if k.startswith("rollout/data_staleness_") or k == "rollout/discarded_unused_trajs"}
+            print(json.dumps({"step": step, **{k: (round(v, 6) if isinstance(v, float) else v)
+                                               for k, v in {**m, **stale}.items() if k in keep or k in stale}}), flush=True)
 
 
 if __name__ == "__main__":

@@ -32,8 +32,9 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 116 /* 0.1.6: bumped whenever an argument struct or a signature changes (0.1.6: rlx_grpo_video_adv, rlx_raw_adv,
-                           * rlx_raw_adv_workspace_bytes; 0.1.5: the development-build query removed;
+#define RLX_VERSION 117 /* 0.1.7: bumped whenever an argument struct or a signature changes (0.1.7: the rollout-store entries
+                           * rlx_version_stats, rlx_gather_rows_segmented, rlx_abi_struct_sizes_ext; 0.1.6: rlx_grpo_video_adv,
+                           * rlx_raw_adv, rlx_raw_adv_workspace_bytes; 0.1.5: the development-build query removed;
                            * 0.1.4: rlx_grpo_dynamic_adv, rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries
                            * rlx_opd_*; round 6: rlx_xgmi_self_timing, the
                            * exchange inside rlx_xgmi_clip_adamw_step under sync_words; round 5: rlx_categorical_sample's
@@ -57,6 +58,9 @@ const char* rlx_last_error(void);
  * token_rows, token_loss_params, copy_segment): a binding written in another language checks its mirrors against these at
  * load time instead of discovering a stale layout through a wrong result.  Writes min(n, 13) entries, returns 13. */
 int rlx_abi_struct_sizes(size_t* sizes, int n);
+/* The same for the structs that came after those 13, in declaration order (version_stats_out, seg_field).  The first list is frozen:
+ * bindings check its length, so structs added later are reported here.  Writes min(n, 2) entries, returns 2. */
+int rlx_abi_struct_sizes_ext(size_t* sizes, int n);
 
 /* Number of compute units / wave size of the current device (plumbing for launch heuristics). */
 int rlx_device_info(int* num_cu, int* wave_size);
@@ -253,6 +257,53 @@ typedef struct rlx_gather_field {
 } rlx_gather_field;
 int rlx_gather_rows(const rlx_gather_field* fields, int n_fields, const int64_t* index, int64_t n_rows,
                     rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The async-PPO rollout store  <- AsyncPPOEmbodiedFSDPActor._drain_received_trajectories / construct_rollout_batch,
+ *   rlinf/workers/actor/async_ppo_fsdp_worker.py:112-182; PriorityStore, rlinf/data/storage/replay/buffer.py:1129-1199;
+ *   convert_trajectories_to_batch, rlinf/data/schema/embodied_types.py:500-559.
+ *
+ * s1 version_stats: one pass over a trajectory's `versions` (f32, n elements) -> a small DEVICE struct the host reads back once
+ *   per added trajectory:  min (bit-equal to torch.min);  sum = the exact integer sum of r = round_half_even(v) (torch.round);
+ *   count[k] = #{r - base == k}, k in [0, n_bins);  below / above = #{r - base < 0} / #{r - base >= n_bins}.
+ *   The store's priority is (min, sum / n), the mean taken on the host in f64; get_metric reads the counts.
+ *   Integer arithmetic in a fixed two-stage tree, no atomics on device memory: two runs give the same bits.
+ *   workspace: rlx_version_stats_workspace_bytes(n) bytes, 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define RLX_VERSION_STATS_MAX_BINS 64
+typedef struct rlx_version_stats_out {
+    float min;
+    int32_t n_bins;
+    int64_t n;
+    int64_t base;
+    int64_t sum;
+    int64_t below;
+    int64_t above;
+    int64_t count[RLX_VERSION_STATS_MAX_BINS];
+} rlx_version_stats_out;
+size_t rlx_version_stats_workspace_bytes(int64_t n);
+int rlx_version_stats(const float* versions, int64_t n, int64_t base, int n_bins, rlx_version_stats_out* out, void* workspace,
+                      size_t workspace_bytes, rlx_stream_t stream);
+
+/* s2 gather_rows_segmented: torch.cat(dim=1) over n_slots stored trajectories, then flatten + row gather, without the
+ *   concatenated copy.  Slot s of a field is a contiguous [t_rows, B_s, row_bytes] block; `srcs` is a HOST table of the n_slots
+ *   device pointers, `slot_envs` a HOST table of the B_s (prefix sums are taken here).  With sumB = sum of B_s:
+ *       dst[i] = slot(b)[t, b - off_s],   j = index ? index[i] : i,  t = j / sumB,  b = j % sumB,  off_s <= b < off_s + B_s.
+ *   index (device, int64, n_rows entries) != NULL: every field gets n_rows rows; an entry outside [0, t_rows * sumB) of a field
+ *   leaves that destination row untouched.  index == NULL: the plain concatenation -- field f gets its own t_rows_f * sumB rows
+ *   (n_rows is ignored), so T-row and T+1-row fields ride in one launch.  A field with one more time row than the index
+ *   addresses (dones, prev_values) is passed as it is: its extra row is simply never addressed.
+ *   16-byte words where every slot pointer, the destination and row_bytes allow, else 8 / 4 / 1.  Bit-exact by construction.
+ * ------------------------------------------------------------------------------------------ */
+#define RLX_STORE_MAX_SLOTS 16
+typedef struct rlx_seg_field {
+    const void* const* srcs;
+    void* dst;
+    int64_t row_bytes;
+    int64_t t_rows;
+} rlx_seg_field;
+int rlx_gather_rows_segmented(const rlx_seg_field* fields, int n_fields, int n_slots, const int64_t* slot_envs,
+                              const int64_t* index, int64_t n_rows, rlx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * a23  clip_adamw_step  <- FSDPModelManager.optimizer_step, rlinf/hybrid_engines/fsdp/fsdp_model_manager.py:429-463

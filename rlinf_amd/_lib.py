@@ -48,6 +48,17 @@ class GatherField(Structure):
 
 
 GATHER_MAX_FIELDS = 16
+STORE_MAX_SLOTS = 16
+VERSION_STATS_MAX_BINS = 64
+
+
+class VersionStats(Structure):  # include/rlx.h: rlx_version_stats_out (a device struct, read back by the host)
+    _fields_ = [("min", c_float), ("n_bins", c_int32), ("n", c_int64), ("base", c_int64), ("sum", c_int64), ("below", c_int64),
+                ("above", c_int64), ("count", c_int64 * VERSION_STATS_MAX_BINS)]
+
+
+class SegField(Structure):  # include/rlx.h: rlx_seg_field
+    _fields_ = [("srcs", POINTER(c_void_p)), ("dst", c_void_p), ("row_bytes", c_int64), ("t_rows", c_int64)]
 ADAMW_MAX_GROUPS = 8
 
 
@@ -154,6 +165,7 @@ PROTOTYPES = {
     "rlx_version": (c_int, []),
     "rlx_last_error": (c_char_p, []),
     "rlx_abi_struct_sizes": (c_int, [c_void_p, c_int]),
+    "rlx_abi_struct_sizes_ext": (c_int, [c_void_p, c_int]),
     "rlx_device_info": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "rlx_done_prefix_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rlx_gae_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -189,6 +201,9 @@ PROTOTYPES = {
     "rlx_mlp_train_bwd": (c_int, [c_void_p, c_void_p, POINTER(MlpLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "rlx_gather_rows": (c_int, [POINTER(GatherField), c_int, c_void_p, c_int64, c_void_p]),
+    "rlx_version_stats_workspace_bytes": (c_size_t, [c_int64]),
+    "rlx_version_stats": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rlx_gather_rows_segmented": (c_int, [POINTER(SegField), c_int, c_int, POINTER(c_int64), c_void_p, c_int64, c_void_p]),
     "rlx_adamw_workspace_bytes": (c_size_t, [c_int64]),
     "rlx_adamw_sync_words": (c_size_t, [c_int64]),
     "rlx_sum_slabs": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -299,7 +314,7 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 116:
+    if lib.rlx_version() < 117:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents
@@ -307,6 +322,14 @@ def load() -> ctypes.CDLL:
     if lib.rlx_abi_struct_sizes(ctypes.cast(sizes, c_void_p), len(mirrors)) != len(mirrors):
         raise RlxError("librlx_hip.so and rlinf_amd/_lib.py disagree on the number of argument structs; rebuild the library")
     for cls, size in zip(mirrors, sizes):
+        if ctypes.sizeof(cls) != size:
+            raise RlxError(f"{cls.__name__}: the ctypes mirror is {ctypes.sizeof(cls)} bytes, the library's struct {size}; "
+                           "rebuild librlx_hip.so (python -m rlinf_amd.csrc.build)")
+    later = (VersionStats, SegField)  # the order rlx_abi_struct_sizes_ext documents
+    sizes = (c_size_t * len(later))()
+    if lib.rlx_abi_struct_sizes_ext(ctypes.cast(sizes, c_void_p), len(later)) != len(later):
+        raise RlxError("librlx_hip.so and rlinf_amd/_lib.py disagree on the number of later argument structs; rebuild the library")
+    for cls, size in zip(later, sizes):
         if ctypes.sizeof(cls) != size:
             raise RlxError(f"{cls.__name__}: the ctypes mirror is {ctypes.sizeof(cls)} bytes, the library's struct {size}; "
                            "rebuild librlx_hip.so (python -m rlinf_amd.csrc.build)")

@@ -310,6 +310,28 @@ def _refuse_foreign_patch_codecs(node, path=""):
         _refuse_foreign_patch_codecs(val, here)
 
 
+def validate_rollout_store_cfg(alg) -> None:
+    """The rollout store of asynchronous PPO (async_ppo_fsdp_worker.py:79-82,106-108,138; the reference's async-PPO page): the
+    defaults keep the store off.  A store larger than one trajectory without a threshold would fail in the reference at the
+    first ``version - None``; here it is refused when the configuration is validated, with the key named."""
+    alg.rollout_store_size_per_rank = int(alg.get("rollout_store_size_per_rank", 1))
+    alg.staleness_threshold = alg.get("staleness_threshold", None)
+    alg.on_policy_min_ratio = float(alg.get("on_policy_min_ratio", 0.0))
+    assert alg.rollout_store_size_per_rank >= 1, "algorithm.rollout_store_size_per_rank must be at least 1"
+    assert alg.rollout_store_size_per_rank <= 16, (
+        "algorithm.rollout_store_size_per_rank must be at most 16 (the slot table of rlx_gather_rows_segmented)")
+    if alg.staleness_threshold is not None:
+        assert alg.staleness_threshold >= 0, "algorithm.staleness_threshold must not be negative"
+    assert 0.0 <= alg.on_policy_min_ratio <= 1.0, "algorithm.on_policy_min_ratio must lie in [0, 1]"
+    if alg.rollout_store_size_per_rank > 1:
+        assert alg.staleness_threshold is not None, (
+            "algorithm.staleness_threshold is required when algorithm.rollout_store_size_per_rank > 1")
+    if alg.rollout_store_size_per_rank > 1 or alg.staleness_threshold is not None:
+        assert alg.loss_type == "decoupled_actor_critic", (
+            "the rollout store (algorithm.rollout_store_size_per_rank / staleness_threshold) belongs to the asynchronous learner: "
+            "algorithm.loss_type must be 'decoupled_actor_critic'")
+
+
 def validate_cfg(cfg) -> DictConfig:
     """Fill defaults and assert consistency; returns the config (rlinf/config.py:1455-1566)."""
     if not isinstance(cfg, DictConfig):
@@ -337,6 +359,7 @@ def validate_cfg(cfg) -> DictConfig:
     alg.logprob_type = alg.get("logprob_type", "action_level")
     alg.entropy_type = alg.get("entropy_type", "action_level")
     alg.bootstrap_type = alg.get("bootstrap_type", "standard")
+    validate_rollout_store_cfg(alg)
     cfg = validate_embodied_cfg(cfg)
     assert cfg.actor.training_backend == "fsdp", "only actor.training_backend='fsdp' (data parallel) is served"
     validate_fsdp_cfg(cfg.actor)

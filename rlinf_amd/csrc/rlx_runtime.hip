@@ -45,6 +45,13 @@ extern "C" int rlx_abi_struct_sizes(size_t* sizes, int n) {
     return count;
 }
 
+extern "C" int rlx_abi_struct_sizes_ext(size_t* sizes, int n) {
+    const size_t all[] = {sizeof(rlx_version_stats_out), sizeof(rlx_seg_field)};
+    const int count = (int)(sizeof(all) / sizeof(all[0]));
+    for (int i = 0; sizes != nullptr && i < n && i < count; ++i) sizes[i] = all[i];
+    return count;
+}
+
 extern "C" int rlx_device_info(int* num_cu_out, int* wave_size) {
     int dev = 0;
     RLX_HIP_CHECK(hipGetDevice(&dev));

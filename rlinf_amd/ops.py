@@ -760,6 +760,82 @@ def gather_rows(fields: list, index: torch.Tensor, outs: Optional[list] = None) 
 
 
 # --------------------------------------------------------------------------------------------
+# s1 / s2  the async-PPO rollout store: version statistics, segmented gather
+# --------------------------------------------------------------------------------------------
+def version_stats_workspace(device) -> tuple:
+    """(device struct, workspace) for version_stats: allocate once, reuse for every added trajectory."""
+    lib = _lib.load()
+    out = torch.zeros(ctypes.sizeof(_lib.VersionStats) // 8, dtype=torch.int64, device=device)
+    ws = torch.empty(lib.rlx_version_stats_workspace_bytes(0) // 8, dtype=torch.int64, device=device)
+    return out, ws
+
+
+def version_stats(versions: torch.Tensor, base: int, n_bins: int = _lib.VERSION_STATS_MAX_BINS, workspace: Optional[tuple] = None
+                  ) -> _lib.VersionStats:
+    """One pass over a trajectory's contiguous f32 ``versions`` -> the host copy of rlx_version_stats_out (min, n, the exact sum
+    of the rounded versions, count[k] of round(v) - base == k, below / above the bin range).  One read-back."""
+    lib = _lib.load()
+    dev = _dev(versions)
+    if versions.dtype != torch.float32 or not versions.is_contiguous():
+        raise RlxError("version_stats needs a contiguous float32 tensor")
+    out, ws = workspace if workspace is not None else version_stats_workspace(dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rlx_version_stats(versions.data_ptr(), versions.numel(), int(base), int(n_bins), out.data_ptr(), ws.data_ptr(),
+                                         ws.numel() * 8, _stream_ptr(dev)), "rlx_version_stats")
+    host = out.cpu()  # the one read-back per added trajectory
+    return _lib.VersionStats.from_buffer_copy(host.numpy().tobytes())
+
+
+def gather_rows_segmented(slot_fields: list, index: Optional[torch.Tensor], outs: Optional[list] = None) -> list:
+    """``slot_fields``: per field the list of its S per-slot tensors, each a contiguous ``[t_rows, B_s, ...]`` block (B_s the same
+    for every field of a slot; t_rows may differ between fields).  -> per field ``cat(slots, dim=1).flatten(0, 1)[index]``, or with
+    ``index=None`` the concatenation itself ``[t_rows, sum B, ...]`` -- one launch per 16 fields, no concatenated intermediate."""
+    lib = _lib.load()
+    if not slot_fields:
+        return []
+    S = len(slot_fields[0])
+    if not 1 <= S <= _lib.STORE_MAX_SLOTS:
+        raise RlxError(f"gather_rows_segmented takes 1..{_lib.STORE_MAX_SLOTS} slots, got {S}")
+    dev = _dev(index, *[t for f in slot_fields for t in f])
+    envs = [int(t.shape[1]) for t in slot_fields[0]]
+    sum_b = sum(envs)
+    for f in slot_fields:
+        if len(f) != S or [int(t.shape[1]) for t in f] != envs:
+            raise RlxError("gather_rows_segmented: every field needs the same per-slot env counts")
+        for t in f:
+            if not t.is_contiguous() or t.shape[0] != f[0].shape[0] or t.shape[2:] != f[0].shape[2:] or t.dtype != f[0].dtype:
+                raise RlxError("gather_rows_segmented needs contiguous [t_rows, B_s, ...] slots of one row shape and dtype per field")
+    if index is not None:
+        if index.dtype != torch.int64:
+            raise RlxError("index must be int64")
+        index = index.contiguous()
+        n = index.numel()
+    else:
+        n = 0
+    if outs is None:
+        outs = [torch.empty((n, *f[0].shape[2:]) if index is not None else (f[0].shape[0], sum_b, *f[0].shape[2:]),
+                            dtype=f[0].dtype, device=dev) for f in slot_fields]
+    env_table = (ctypes.c_int64 * S)(*envs)
+    with torch.cuda.device(dev):
+        for lo in range(0, len(slot_fields), _lib.GATHER_MAX_FIELDS):
+            chunk = list(zip(slot_fields, outs))[lo:lo + _lib.GATHER_MAX_FIELDS]
+            arr, tables, k = (_lib.SegField * len(chunk))(), [], 0
+            for f, dst in chunk:
+                row_bytes = f[0].element_size() * (f[0][0, 0].numel() if f[0].dim() > 2 else 1)
+                if row_bytes == 0 or f[0].shape[0] == 0:
+                    continue
+                if not dst.is_contiguous():
+                    raise RlxError("gather_rows_segmented needs contiguous destinations")
+                tables.append((ctypes.c_void_p * S)(*[t.data_ptr() for t in f]))
+                arr[k].srcs, arr[k].dst, arr[k].row_bytes, arr[k].t_rows = tables[-1], dst.data_ptr(), row_bytes, f[0].shape[0]
+                k += 1
+            if k and (index is None or n):
+                _lib.check(lib.rlx_gather_rows_segmented(arr, k, S, env_table, _ptr(index), n, _stream_ptr(dev)),
+                           "rlx_gather_rows_segmented")
+    return outs
+
+
+# --------------------------------------------------------------------------------------------
 # a23  clip + AdamW on flat buffers
 # --------------------------------------------------------------------------------------------
 def actor_param_ranges(layout: MlpLayout) -> list:

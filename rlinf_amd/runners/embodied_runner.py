@@ -63,6 +63,13 @@ class EmbodiedRunner:
                                if getattr(h, "worker", None) is not None), None)
         self.split = self.placement is not None and bool(getattr(self.placement, "split", False))
         self._landing = None  # the learner rank's persistent landing buffer for shipped trajectories
+        # asynchronous PPO's rollout store (workers/actor/async_ppo_fsdp_worker.py): a training round may take several rollouts,
+        # sampled with the weights the rollout worker last received and stamped with THEIR version
+        alg = cfg.get("algorithm", None) or {}
+        self.use_rollout_store = (alg.get("loss_type", None) == "decoupled_actor_critic"
+                                  and (int(alg.get("rollout_store_size_per_rank", 1)) > 1
+                                       or alg.get("staleness_threshold", None) is not None))
+        self.rollout_count = 0
 
     def set_max_steps(self):
         r = self.cfg.runner
@@ -83,6 +90,10 @@ class EmbodiedRunner:
         learner's policy object in the collocated rollout worker (no copy on weight sync), inject pre-generated env tensors."""
         if not share_weights:
             self.cfg.rollout.share_actor_weights = False
+        if self.use_rollout_store:
+            assert not self.split, "the rollout store is served with the collocated placement (the receive thread is Ray-side)"
+            if self.weight_sync_interval > 1:  # the rollout worker keeps sampling with the weights it last received: its own copy
+                self.cfg.rollout.share_actor_weights = False
         rollout_handle = self.rollout.init_worker()
         env_handle = self.env.init_worker(env_tensors)
         if self.reward is not None:
@@ -196,17 +207,21 @@ class EmbodiedRunner:
         if hasattr(worker, "defer_host_reads"):
             worker.defer_host_reads = bool(defer)
         self.actor.set_global_step(self.global_step).wait()
-        self.rollout.set_global_step(self.global_step).wait()
-        if step % self.weight_sync_interval == 0:
-            self.update_rollout_weights()
-        env_handle = self.env.interact(input_channel=self.env_channel, rollout_channel=self.rollout_channel,
-                                       reward_channel=self.reward_channel, actor_channel=self.actor_channel, eps=eps)
-        rollout_handle = self.rollout.generate(input_channel=self.rollout_channel, output_channel=self.env_channel)
-        if self.split:
-            self._ship_trajectories()
-        self.actor.recv_rollout_trajectories(input_channel=self.actor_channel).wait()
-        rollout_handle.wait()
-        env_handle.wait()
+        staleness_metrics = {}
+        if self.use_rollout_store:
+            staleness_metrics = self._fill_rollout_store(eps)
+        else:
+            self.rollout.set_global_step(self.global_step).wait()
+            if step % self.weight_sync_interval == 0:
+                self.update_rollout_weights()
+            env_handle = self.env.interact(input_channel=self.env_channel, rollout_channel=self.rollout_channel,
+                                           reward_channel=self.reward_channel, actor_channel=self.actor_channel, eps=eps)
+            rollout_handle = self.rollout.generate(input_channel=self.rollout_channel, output_channel=self.env_channel)
+            if self.split:
+                self._ship_trajectories()
+            self.actor.recv_rollout_trajectories(input_channel=self.actor_channel).wait()
+            rollout_handle.wait()
+            env_handle.wait()
         rollout_metrics = self.actor.compute_advantages_and_returns().wait()[0]
         actor_training_handle = self.actor.run_training()
         env_bootstrap_handle = None
@@ -229,6 +244,7 @@ class EmbodiedRunner:
             dt = (now - self._last_landed) if (defer and self._last_landed is not None) else now - t0
             self._last_landed = now
             metrics = {f"rollout/{k}": v for k, v in rm.items()}
+            metrics.update({f"rollout/{k}": v for k, v in staleness_metrics.items()})  # async_ppo_embodied_runner.py:197-204
             metrics.update({f"train/{k}": v for k, v in tm.items()})
             metrics.update(eval_metrics)
             metrics.update({"time/step": dt, "perf/env_steps_per_sec": env_steps / dt})
@@ -242,6 +258,44 @@ class EmbodiedRunner:
             return finish()
         eval_metrics = self._maybe_eval_and_checkpoint(step)  # (evaluation / checkpoints read the device: they wait by themselves)
         return PendingStep(finish)
+
+    def _sync_rollout_weights(self):
+        """Weights to the rollout worker, which from now on stamps its trajectories with this version."""
+        self.update_rollout_weights()
+        self.rollout.set_global_step(self.global_step).wait()
+        self._rollout_synced = True
+
+    def _fill_rollout_store(self, eps=None) -> dict:
+        """The rollout side of one asynchronous-PPO training round in one process (async_ppo_embodied_runner.py:109-163 runs it
+        concurrently): roll out and hand the trajectory to the learner until its store is ready, then return the store's staleness
+        metrics.  The rollout worker samples with the weights it last received -- synced every ``runner.weight_sync_interval``
+        training rounds -- and stamps trajectories with that version.  The reference's run-ahead bound
+        (async_huggingface_worker.py:93-100) holds: no rollout starts whose version would be more than ``staleness_threshold``
+        behind ``version + 1``; a weight sync is forced instead.  ``eps``: a tensor for the round's first rollout, or a function of
+        the running rollout count."""
+        a, step = self.actor.worker, self.global_step
+        threshold, size = a.staleness_threshold, a.rollout_store_size
+        sync = step % self.weight_sync_interval == 0 or not getattr(self, "_rollout_synced", False)
+        for _ in range(2 * size + 2):
+            if sync or step + 1 - int(self.rollout.worker.version) > threshold:
+                self._sync_rollout_weights()
+            draws = eps(self.rollout_count) if callable(eps) else eps
+            env_handle = self.env.interact(input_channel=self.env_channel, rollout_channel=self.rollout_channel,
+                                           reward_channel=self.reward_channel, actor_channel=self.actor_channel, eps=draws)
+            rollout_handle = self.rollout.generate(input_channel=self.rollout_channel, output_channel=self.env_channel)
+            self.rollout_count += 1
+            self.actor.recv_rollout_trajectories(input_channel=self.actor_channel).wait()
+            rollout_handle.wait()
+            env_handle.wait()
+            metrics = self.actor.construct_rollout_batch().wait()[0]
+            if metrics is not None:
+                return metrics
+            # enough trajectories but too few on-policy cells: the next rollout is sampled with the current weights
+            sync = len(a.rollout_store) >= size
+            if not callable(eps):
+                eps = None
+        raise RuntimeError(f"the rollout store was not ready after {2 * size + 2} rollouts (store size {size}, staleness_threshold "
+                           f"{threshold}, on_policy_min_ratio {a.on_policy_min_ratio}): the configuration cannot be satisfied")
 
     def run(self, eps_fn=None):
         """``runner.defer_metrics`` (default true): iterations are queued one ahead of the metrics being read (see run_step)."""

@@ -6,8 +6,15 @@ What differs from the synchronous learner (embodied_fsdp_actor_worker.py) is dat
 policy ``versions`` they were sampled with; the loss is ``decoupled_actor_critic`` (clip against a proximal policy given,
 recomputed, or interpolated from the version distance; importance-weight by exp(proximal - behaviour)); advantages are
 normalised a second time over the whole shuffled buffer with cross-rank statistics (``masked_normalization``); dual clip is
-on by default (clip_ratio_c 3.0).  The reference's receive thread, rollout store and staleness bookkeeping (:84-183) are
-control plane and not mirrored: ``recv_rollout_trajectories`` of the base class fills ``rollout_batch`` directly.
+on by default (clip_ratio_c 3.0).
+
+The rollout store (:72-182) is mirrored when ``algorithm.rollout_store_size_per_rank > 1`` or ``algorithm.staleness_threshold``
+is set: received trajectories are snapshot into a ``PriorityStore`` (data/rollout_store.py), dropped on receipt and evicted
+before every round when staler than the threshold, and a round trains on ``topn(store_size)`` -- assembled by
+``rlx_gather_rows_segmented`` straight from the store's slots, so ``versions`` genuinely varies per row.  Without those keys
+``recv_rollout_trajectories`` of the base class fills ``rollout_batch`` directly and no store exists.  The reference's receive
+thread and channel drain are Ray-side control plane and not mirrored: ``construct_rollout_batch`` returns None ("not ready")
+instead of sleeping, and the runner answers with another rollout.
 """
 
 from __future__ import annotations
@@ -26,6 +33,85 @@ from .embodied_fsdp_actor_worker import CRITIC_EXPLAINED_VARIANCE_KEY, EmbodiedF
 class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
     """Embodied learner for async PPO / decoupled actor-critic training."""
 
+    def __init__(self, cfg, ctx=None):
+        super().__init__(cfg, ctx)
+        alg = cfg.algorithm
+        self.rollout_store_size = int(alg.get("rollout_store_size_per_rank", 1))  # :79-82
+        self.staleness_threshold = alg.get("staleness_threshold", None)
+        self.on_policy_min_ratio = float(alg.get("on_policy_min_ratio", 0.0))
+        self.use_rollout_store = self.rollout_store_size > 1 or self.staleness_threshold is not None
+        self.rollout_store = None
+        self.dropped_on_receipt = 0
+        if self.use_rollout_store:
+            assert self.staleness_threshold is not None, (
+                "algorithm.staleness_threshold is required when algorithm.rollout_store_size_per_rank > 1")
+            assert self.pipeline_epochs == 1, "the rollout store is not served together with runner.use_training_pipeline epochs"
+            from ...data.rollout_store import PriorityStore
+            self.rollout_store = PriorityStore(maxsize=self.rollout_store_size)
+
+    # ---- the rollout store (:84-182) ---------------------------------------------------------------------------------------------
+    def recv_rollout_trajectories(self, input_channel=None):
+        """:99-128 without the thread: every received trajectory is snapshot into the store's spare slot, its (min, mean, histogram)
+        taken in one device pass, and it is dropped when its minimum version is below ``version - staleness_threshold``."""
+        if not self.use_rollout_store:
+            return super().recv_rollout_trajectories(input_channel)
+        if isinstance(input_channel, (list, tuple)):
+            trajectories = list(input_channel)
+        else:
+            trajectories = []
+            while not input_channel.empty():
+                trajectories.append(input_channel.get())
+        for traj in trajectories:
+            staged = self.rollout_store.stage(traj)
+            if staged.summary.min < self.version - self.staleness_threshold:
+                self.dropped_on_receipt += 1
+                self.rollout_store.discard(staged)
+                continue
+            self.rollout_store.add(staged.summary.priority, staged)
+
+    def rollout_store_ready(self) -> bool:
+        """One pass of _wait_for_rollout_store_ready's loop body (:139-159): evict below the threshold, then enough trajectories
+        and, with ``on_policy_min_ratio``, that share of the stored cells at the current version."""
+        store = self.rollout_store
+        store.remove_below(self.version - self.staleness_threshold)
+        if len(store) < self.rollout_store_size:
+            return False
+        if self.on_policy_min_ratio <= 0.0:
+            return True
+        return store.get_metric().get(int(self.version), {}).get("ratio", 0.0) >= self.on_policy_min_ratio
+
+    def construct_rollout_batch(self):
+        """:161-182.  None when the store is not ready (the runner then rolls out again); else the staleness metrics of the
+        store, with ``rollout_batch`` assembled from ``topn(store_size)``."""
+        assert self.use_rollout_store, "construct_rollout_batch needs the rollout store (algorithm.staleness_threshold)"
+        if not self.rollout_store_ready():
+            return None
+        slots = self.rollout_store.topn(self.rollout_store_size)
+        staleness_metrics: dict = {}
+        for version_val, stats in self.rollout_store.get_metric().items():
+            if version_val == "discarded_unused":
+                staleness_metrics["discarded_unused_trajs"] = stats
+                continue
+            staleness_metrics[f"data_staleness_{int(self.version) - int(version_val)}/ratio"] = stats["ratio"]
+        self.rollout_batch = self._process_received_rollout_batch(self._assemble_store_batch(slots))
+        return staleness_metrics
+
+    def _assemble_store_batch(self, slots: list) -> dict:
+        """convert_trajectories_to_batch (embodied_types.py:500-559) for the arrays the advantage and metric kernels want
+        contiguous -- rewards [T, sum B], dones and prev_values [T + 1, sum B] -- in one segmented launch into persistent buffers.
+        The large fields stay in the slots (``_store``): run_training gathers its shuffled rows straight from them."""
+        T, B = slots[0].rewards.shape[:2]
+        sum_b = B * len(slots)
+        key = ("store_batch", T, sum_b)
+        names = ("rewards", "dones", "prev_values")
+        if key not in self._ws:
+            self._ws[key] = [torch.empty((getattr(slots[0], n).shape[0], sum_b, *getattr(slots[0], n).shape[2:]),
+                                         dtype=getattr(slots[0], n).dtype, device=self.device) for n in names]
+        outs = ops.gather_rows_segmented([[getattr(s, n) for s in slots] for n in names], None, self._ws[key])
+        batch = dict(zip(names, outs))
+        batch["_store"] = {"slots": slots, "T": int(T), "B": int(sum_b)}
+        return batch
+
     def compute_advantages_and_returns(self) -> dict:
         """:185-213 -- GAE against the proximal values when the batch carries them."""
         alg, b = self.cfg.algorithm, self.rollout_batch
@@ -42,6 +128,20 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
     def compute_proximal_logprobs(self) -> None:
         """:215-272 -- log-probs of the stored actions under the CURRENT weights, in micro-batch sized pieces, un-shuffled."""
         b, m = self.rollout_batch, self.model
+        if "_store" in b:  # per slot, into a slot-shaped buffer: it rides with the other large fields in the segmented gather
+            step = int(self.cfg.actor.micro_batch_size)
+            for i, s in enumerate(b["_store"]["slots"]):
+                n = s.prev_logprobs.shape[0] * s.prev_logprobs.shape[1]
+                key = ("store_prox", i, tuple(s.prev_logprobs.shape))
+                if key not in self._ws:
+                    self._ws[key] = torch.empty_like(s.prev_logprobs)
+                out = self._ws[key].view(n, -1)
+                states, action = s.forward_inputs["states"].view(n, -1), s.forward_inputs["action"].view(n, -1)
+                for lo in range(0, n, step):
+                    out[lo:lo + step] = ops.mlp_train_fwd(m.flat.data, m.packed(), m.layout, states[lo:lo + step], action[lo:lo + step])[0]
+            b["_store"]["proximal_logprobs"] = [self._ws[("store_prox", i, tuple(s.prev_logprobs.shape))]
+                                                for i, s in enumerate(b["_store"]["slots"])]
+            return
         T, B = b["prev_logprobs"].shape[:2]
         states = b["forward_inputs"]["states"].reshape(T * B, -1)
         action = b["forward_inputs"]["action"].reshape(T * B, -1)
@@ -57,13 +157,16 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
         """flatten_rollout_batch_for_train (:42-69) with one randperm seeded actor.seed + rank (:283-285), then
         masked_normalization of the advantages over the whole buffer, statistics summed over ranks (:292-296)."""
         b = self.rollout_batch
-        T, B = b["prev_logprobs"].shape[:2]
+        store = b.get("_store")
+        T, B = (store["T"], store["B"]) if store is not None else b["prev_logprobs"].shape[:2]
         N = T * B
         pkey = ("perm", N)
         if pkey not in self._ws:
             g = torch.Generator()
             g.manual_seed(int(self.cfg.actor.seed) + self._rank)
             self._ws[pkey] = torch.randperm(N, generator=g).to(self.device)
+        if store is not None:
+            return self._flatten_shuffle_normalize_store(b, store, N, self._ws[pkey])
         fields = {"states": b["forward_inputs"]["states"], "action": b["forward_inputs"]["action"],
                   "prev_logprobs": b["prev_logprobs"], "advantages": b["advantages"], "prev_values": b["prev_values"][:-1],
                   "returns": b.get("returns"), "loss_mask": b.get("loss_mask"), "versions": b.get("versions"),
@@ -81,14 +184,44 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
             self._ws[key] = [torch.empty_like(t) for t in src] + [torch.empty(N, *src[list(fields).index("advantages")].shape[1:],
                                                                               dtype=torch.float32, device=self.device)]
         flat = dict(zip(fields, ops.gather_rows(src, self._ws[pkey], self._ws[key][:-1])))
+        return self._normalize_flat_advantages(flat, self._ws[key][-1]), N
+
+    def _flatten_shuffle_normalize_store(self, b: dict, store: dict, N: int, perm: torch.Tensor):
+        """The same rows from a store batch: the fields that live in the slots (states, action, prev_logprobs, versions,
+        prev_values, proximal log-probs when recomputed) come out of ONE segmented launch -- cat(dim=1) + flatten + gather without
+        the concatenated copy; the arrays computed on the assembled batch (advantages, returns, masks) through rlx_gather_rows."""
+        slots = store["slots"]
+        seg = {"states": [s.forward_inputs["states"] for s in slots], "action": [s.forward_inputs["action"] for s in slots],
+               "prev_logprobs": [s.prev_logprobs for s in slots], "versions": [s.versions for s in slots],
+               "prev_values": [s.prev_values for s in slots]}  # (T + 1 rows: the closing row is never addressed)
+        if store.get("proximal_logprobs") is not None:
+            seg["proximal_logprobs"] = store["proximal_logprobs"]
+        cont = {"advantages": b["advantages"], "returns": b.get("returns"), "loss_mask": b.get("loss_mask"),
+                "proximal_values": b.get("proximal_values")[:-1] if b.get("proximal_values") is not None else None}
+        if b.get("loss_mask_sum") is not None:
+            cont["loss_mask_sum"] = b["loss_mask_sum"].contiguous()
+        cont = {k: v for k, v in cont.items() if v is not None}
+        src = [v.reshape(N, *v.shape[2:]).contiguous() for v in cont.values()]
+        key = ("ashuf_store", N, tuple((n, tuple(f[0].shape[2:]), f[0].dtype) for n, f in seg.items()),
+               tuple((n, tuple(t.shape[1:]), t.dtype) for n, t in zip(cont, src)))
+        if key not in self._ws:
+            adv = src[list(cont).index("advantages")]
+            self._ws[key] = ([torch.empty((N, *f[0].shape[2:]), dtype=f[0].dtype, device=self.device) for f in seg.values()],
+                             [torch.empty_like(t) for t in src], torch.empty(N, *adv.shape[1:], dtype=torch.float32, device=self.device))
+        seg_out, cont_out, adv_out = self._ws[key]
+        flat = dict(zip(seg, ops.gather_rows_segmented(list(seg.values()), perm, seg_out)))
+        flat.update(zip(cont, ops.gather_rows(src, perm, cont_out)))
+        return self._normalize_flat_advantages(flat, adv_out), N
+
+    def _normalize_flat_advantages(self, flat: dict, out: torch.Tensor) -> dict:
         if self.cfg.algorithm.get("normalize_advantages", True):
             adv, mask = flat["advantages"], flat.get("loss_mask")
             if mask is not None:
                 assert mask.dim() == adv.dim() and mask.shape == adv.shape, (mask.shape, adv.shape)
             stats = ops.masked_stats(adv, mask)
             all_reduce_flat_(stats, self.ctx)  # factor, x_sum, x_sum_sq in ONE call (the reference issues three)
-            flat["advantages"] = ops.masked_normalize(adv, mask, stats, out=self._ws[key][-1])
-        return flat, N
+            flat["advantages"] = ops.masked_normalize(adv, mask, stats, out=out)
+        return flat
 
     # ---- the fused path: rlx_ppo_step with the decoupled loss + deferred actor scale, prepared launches, hipGraph -------
     def _fused_update_ok(self, flat: dict) -> bool:
