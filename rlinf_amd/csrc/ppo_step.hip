@@ -90,7 +90,7 @@ __device__ __forceinline__ void mfma_step(const f32x4 (&a)[RT], const f32x4 (&b)
 // (History, measured on MI355X: weight chunks staged through LDS with a barrier per chunk left the matrix pipe 36 % busy;
 //  row-major weights read as 16 rows x 64 B per instruction cost 75 of 122 us in load issue; a "k < K ? load : 0"
 //  tail select made hipcc serialise 64 L2 round trips.)
-template <int RT, int NW, int PD, int ABL>
+template <int RT, int NW, int PD>
 struct RowGemm {
     typedef Geo<RT, NW> G;
     static constexpr int CT = G::CT, KI = 32, MAXIT = HID / KI;
@@ -105,10 +105,7 @@ struct RowGemm {
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                if constexpr (ABL & ABL_NO_WLOAD) b[h][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                else b[h][ct] = *reinterpret_cast<const f32x4*>(wbase + ((size_t)(ct * nit + itx) * 2 + h) * 256);
-            }
+            for (int ct = 0; ct < CT; ++ct) b[h][ct] = *reinterpret_cast<const f32x4*>(wbase + ((size_t)(ct * nit + itx) * 2 + h) * 256);
     }
     // Issue the first PD iterations of weight loads for matrix P.  Call it BEFORE the epilogue that produces the GEMM's
     // input: the weights do not depend on it, so their L2 / Infinity-Cache latency hides behind the tanh sweep.
@@ -134,14 +131,7 @@ struct RowGemm {
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt)
                     a[rt] = *reinterpret_cast<const f32x4*>(X + (rt * 16 + r16) * XS + it * KI + 16 * h + 4 * kq);
-                if constexpr (ABL & ABL_NO_MFMA) {
-#pragma unroll
-                    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] += a[rt] * bq[it % PD][h][ct];
-                } else {
-                    mfma_step(a, bq[it % PD][h], acc);
-                }
+                mfma_step(a, bq[it % PD][h], acc);
             }
             if (it + PD < nit) {
                 gload(it + PD, bq[it % PD]);
@@ -153,10 +143,9 @@ struct RowGemm {
 };
 
 // coalesced copy of the slab's first 256 columns to a row-major [M][256] global array (1 KiB per row)
-template <int RT, int NW, int ABL = 0>
+template <int RT, int NW>
 __device__ __forceinline__ void flush_rows(const float* X, float* __restrict__ dst, long long m0, long long M) {
     typedef Geo<RT, NW> G;
-    if constexpr (ABL & ABL_NO_FLUSH) return;
     for (int f = threadIdx.x; f < G::BM * 64; f += G::NT) {
         const int row = f >> 6, c4 = (f & 63) * 4;
         if (m0 + row < M) *reinterpret_cast<f32x4*>(dst + (size_t)(m0 + row) * HID + c4) = *reinterpret_cast<const f32x4*>(X + row * XS + c4);
@@ -184,7 +173,7 @@ __device__ __forceinline__ void load_states(const float* __restrict__ states, fl
 }
 
 // forward hidden-layer epilogue: h = tanh(acc + bias) -> slab (in place); KEEP: remember 1 - h^2 per element
-template <int RT, int NW, bool KEEP, int ABL = 0>
+template <int RT, int NW, bool KEEP>
 __device__ __forceinline__ void epilogue_tanh(const f32x4 (&acc)[RT][Geo<RT, NW>::CT], const float* __restrict__ bias, float* X,
                                               f32x4 (*kept)[Geo<RT, NW>::CT]) {
     typedef Geo<RT, NW> G;
@@ -198,7 +187,7 @@ __device__ __forceinline__ void epilogue_tanh(const f32x4 (&acc)[RT][Geo<RT, NW>
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float z = acc[rt][ct][r] + b;
-                const float h = (ABL & ABL_NO_TANH) ? fminf(fmaxf(z, -1.f), 1.f) : fast_tanh(z);
+                const float h = fast_tanh(z);
                 X[(rt * 16 + 4 * kq + r) * XS + col] = h;
                 if constexpr (KEEP) kept[rt][ct][r] = 1.f - h * h;
             }
@@ -249,30 +238,21 @@ __global__ __launch_bounds__(512) void rollout_step_kernel(RolloutArgs a) {
         if (job == 2) b -= a.tiles_vj0;
         y = 0; m0 = (long long)b * G::BM; M = a.vj[job - 1].m; states = a.vj[job - 1].states;
     }
-    Stamps ts{a.stamps, 0};
-    ts.mark();
     const int n_out = y == 1 ? lay.act_dim : lay.val_dim;
-    RowGemm<RT, NW, PD, 0> gemm;
+    RowGemm<RT, NW, PD> gemm;
     gemm.prefetch(a.tiles + Tiles::mat(y, 0), Tiles::K1P / 32);
     load_states<RT, NW>(states, states_copy, D, m0, M, X);
     stage_head(a.params + lay.off_w[y][3], lay.off_b[y][3] >= 0 ? a.params + lay.off_b[y][3] : nullptr, n_out, W4s, b4s, G::NT);
     lds_barrier();
-    ts.mark();
     f32x4 acc[RT][G::CT];
     gemm.run(X, acc);
     gemm.prefetch(a.tiles + Tiles::mat(y, 1), HID / 32);
-    ts.mark();
     epilogue_tanh<RT, NW, false>(acc, a.params + lay.off_b[y][0], X, nullptr);
-    ts.mark();
     gemm.run(X, acc);
     gemm.prefetch(a.tiles + Tiles::mat(y, 2), HID / 32);
-    ts.mark();
     epilogue_tanh<RT, NW, false>(acc, a.params + lay.off_b[y][1], X, nullptr);
-    ts.mark();
     gemm.run(X, acc);
-    ts.mark();
     epilogue_tanh<RT, NW, false>(acc, a.params + lay.off_b[y][2], X, nullptr);
-    ts.mark();
 
     for (int idx = tid; idx < G::BM * n_out; idx += G::NT) {
         const int row = idx / n_out, o = idx % n_out;
@@ -296,7 +276,6 @@ __global__ __launch_bounds__(512) void rollout_step_kernel(RolloutArgs a) {
             value_job_output(a.vj[job - 1], g, (size_t)(m0 + row), o, s);
         }
     }
-    ts.mark();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -304,7 +283,7 @@ __global__ __launch_bounds__(512) void rollout_step_kernel(RolloutArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 // OP: head outputs padded to 8 or 16 (compile time): the loops over head outputs run unpredicated on zero padding --
 // a runtime "o < n_out" guard around an LDS read serialises every read behind its own lgkmcnt(0).
-template <int RT, int NW, int PD, int ABL, int OP, bool DEC = false>  // DEC: the decoupled actor loss (StepArgs.dec)
+template <int RT, int NW, int PD, int OP, bool DEC = false>  // DEC: the decoupled actor loss (StepArgs.dec)
 __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
     typedef Geo<RT, NW> G;
     constexpr int BM = G::BM, CT = G::CT;
@@ -340,36 +319,27 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
     }
 
     // ---- forward -----------------------------------------------------------------------------------------------------
-    Stamps ts{a.stamps, 0};
-    ts.mark();
-    RowGemm<RT, NW, PD, ABL> gemm;
+    RowGemm<RT, NW, PD> gemm;
     gemm.prefetch(a.tiles + Tiles::mat(y, 0), Tiles::K1P / 32);
     load_states<RT, NW>(a.states, nullptr, D, m0, M, X);
     stage_head(a.params + lay.off_w[y][3], lay.off_b[y][3] >= 0 ? a.params + lay.off_b[y][3] : nullptr, n_out, W4s, b4s, G::NT);
     for (int i = tid; i < BM * MAX_OUT; i += G::NT) sHead[i] = 0.f;                       // zero padding for o >= n_out
     for (int i = n_out * W4S + tid; i < OP * W4S; i += G::NT) W4s[i] = 0.f;
     lds_barrier();
-    ts.mark();
     f32x4 acc[RT][CT];
     f32x4 kept[3][RT][CT];  // 1 - h_l^2 in the accumulator layout: the backward epilogues need exactly these lanes
     float* hy = a.h + (size_t)(y * 2) * M * HID;
     float* dzy = a.dz + (size_t)(y * 3) * M * HID;
     gemm.run(X, acc);
     gemm.prefetch(a.tiles + Tiles::mat(y, 1), HID / 32);
-    ts.mark();
-    epilogue_tanh<RT, NW, true, ABL>(acc, a.params + lay.off_b[y][0], X, kept[0]);
-    flush_rows<RT, NW, ABL>(X, hy, m0, M);
-    ts.mark();
+    epilogue_tanh<RT, NW, true>(acc, a.params + lay.off_b[y][0], X, kept[0]);
+    flush_rows<RT, NW>(X, hy, m0, M);
     gemm.run(X, acc);
     gemm.prefetch(a.tiles + Tiles::mat(y, 2), HID / 32);
-    ts.mark();
-    epilogue_tanh<RT, NW, true, ABL>(acc, a.params + lay.off_b[y][1], X, kept[1]);
-    flush_rows<RT, NW, ABL>(X, hy + (size_t)M * HID, m0, M);
-    ts.mark();
+    epilogue_tanh<RT, NW, true>(acc, a.params + lay.off_b[y][1], X, kept[1]);
+    flush_rows<RT, NW>(X, hy + (size_t)M * HID, m0, M);
     gemm.run(X, acc);
-    ts.mark();
-    epilogue_tanh<RT, NW, true, ABL>(acc, a.params + lay.off_b[y][2], X, kept[2]);
-    ts.mark();
+    epilogue_tanh<RT, NW, true>(acc, a.params + lay.off_b[y][2], X, kept[2]);
 
     // ---- head + loss element math ---------------------------------------------------------------------------------------
     const double nm = has_mask ? sNm[0] : 0.0;
@@ -468,7 +438,6 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
         }
     }
     lds_barrier();
-    ts.mark();
 
     // ---- head parameter gradients, per 32-row half tile (h3 is still in the slab): thread = (half, hidden column j) ----
     for (int u = tid; u < (BM / 32) * HID; u += G::NT) {
@@ -500,7 +469,6 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
             part[n_out * HID + n_out + j] = y == 1 ? sl : 0.f;
         }
     }
-    ts.mark();
 
     // ---- dZ3 = (dOut . W4) * (1 - h3^2), in the accumulator layout, into the slab ---------------------------------------
     gemm.prefetch(a.tiles + Tiles::mat(y, 4), HID / 32);  // W3^T tiles for the first backward GEMM
@@ -533,8 +501,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) X[(rt * 16 + 4 * kq + r) * XS + wave * 16 * CT + ct * 16 + r16] = acc[rt][ct][r];
     lds_barrier();
-    flush_rows<RT, NW, ABL>(X, dzy + 2 * (size_t)M * HID, m0, M);
-    ts.mark();
+    flush_rows<RT, NW>(X, dzy + 2 * (size_t)M * HID, m0, M);
 
     // ---- backward-data chain -------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -549,10 +516,8 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
                 for (int r = 0; r < 4; ++r)
                     X[(rt * 16 + 4 * kq + r) * XS + wave * 16 * CT + ct * 16 + r16] = acc[rt][ct][r] * kept[l - 1][rt][ct][r];
         lds_barrier();
-        flush_rows<RT, NW, ABL>(X, dzy + (size_t)(l - 1) * M * HID, m0, M);
-        ts.mark();
+        flush_rows<RT, NW>(X, dzy + (size_t)(l - 1) * M * HID, m0, M);
     }
-    ts.mark();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -562,44 +527,8 @@ __global__ __launch_bounds__(64 * NW) void ppo_step_fused_kernel(StepArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int frag_row32(int r, int khalf) { return (r & 3) + 8 * (r >> 2) + 4 * khalf; }
 
-// ---- f32 products on the bf16 matrix pipe ("3 x bf16 split") ------------------------------------------------------------
-// An f32 number is EXACTLY hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (3 x 8 significand bits,
-// the differences are exact in f32: tests/test_bf16_split_exact.py), and a product of two bf16 numbers is exact in f32.  So
-// a . b = sum over the nine partial products; the six kept here -- hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid -- leave out terms
-// below 2^-24 of |a||b| (mid.lo, lo.mid, lo.lo), i.e. below the rounding of the f32 accumulation itself.  Six
-// v_mfma_f32_32x32x16_bf16 (32 cycles each for K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each for K = 2): 2.7 x less
-// matrix-pipe time for the same f32-level accuracy -- the f32 MFMA rate of this part is 1/16 of its bf16 rate.  The operand
-// split runs on the VALU (packed converts), next to the matrix pipe.
-typedef __bf16 dw_bf16x8 __attribute__((ext_vector_type(8)));
-struct DwSplit3 {
-    dw_bf16x8 hi, mid, lo;
-};
-__device__ __forceinline__ DwSplit3 dw_split3(const float (&w)[8]) {
-    DwSplit3 q;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)w[j];
-        const float r1 = fsub(w[j], (float)h);
-        const __bf16 m = (__bf16)r1;
-        const float r2 = fsub(r1, (float)m);
-        q.hi[j] = h;
-        q.mid[j] = m;
-        q.lo[j] = (__bf16)r2;
-    }
-    return q;
-}
-__device__ __forceinline__ f32x16 dw_mfma6(const DwSplit3& a, const DwSplit3& b, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);   // smallest terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid, b.mid, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid, b.hi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.mid, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.hi, acc, 0, 0, 0);
-}
-
-// SPLIT: the products run as 3 x bf16 splits on v_mfma_f32_32x32x16_bf16 (default); false: exact f32 products on
-// v_mfma_f32_32x32x2_f32 (RLX_F32_EXACT_MFMA=1).
-template <bool SPLIT>
+// Exact f32 products on v_mfma_f32_32x32x2_f32.  Reached only under RLX_F32_EXACT_MFMA=1: the default precision-"32" weight
+// gradients run on the bf16 matrix pipe with three-plane operands (ppo_step_dw_f32x_kernel, ppo_step_f32x.hip).
 __global__ __launch_bounds__(256, 2) void ppo_step_dw_kernel(DwArgs a) {
     __shared__ __align__(16) float As[2][32][128];
     __shared__ __align__(16) float Bs[2][32][128];
@@ -691,44 +620,17 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_kernel(DwArgs a) {
     for (int c = 0; c < nchunks; ++c) {
         const int cur = c & 1;
         if (c + 1 < nchunks) gload(c + 1);
-        if constexpr (SPLIT) {
-            // two 16-k blocks per 32-row chunk; lane (column lrow, k group khalf) holds k = 16 kb + 8 khalf + j, j = 0 .. 7 of its
-            // column for A and for B alike (K is only the summation index: the slots just have to pair up)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                float af[2][8], bf[2][8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * kb + 8 * khalf + j;
-                    af[0][j] = As[cur][k][wi * 64 + lrow];
-                    af[1][j] = As[cur][k][wi * 64 + 32 + lrow];
-                    bf[0][j] = Bs[cur][k][wj * 64 + lrow];
-                    bf[1][j] = Bs[cur][k][wj * 64 + 32 + lrow];
-                }
-                const DwSplit3 A0 = dw_split3(af[0]), A1 = dw_split3(af[1]), B0 = dw_split3(bf[0]), B1 = dw_split3(bf[1]);
-                acc[0][0] = dw_mfma6(A0, B0, acc[0][0]);
-                acc[0][1] = dw_mfma6(A0, B1, acc[0][1]);
-                acc[1][0] = dw_mfma6(A1, B0, acc[1][0]);
-                acc[1][1] = dw_mfma6(A1, B1, acc[1][1]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    bsum[0] += af[0][j];
-                    bsum[1] += af[1][j];
-                }
-            }
-        } else {
 #pragma unroll 4
-            for (int kp = 0; kp < 16; ++kp) {
-                const int k = 2 * kp + khalf;
-                const float a0 = As[cur][k][wi * 64 + lrow], a1 = As[cur][k][wi * 64 + 32 + lrow];
-                const float b0 = Bs[cur][k][wj * 64 + lrow], b1 = Bs[cur][k][wj * 64 + 32 + lrow];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-                bsum[0] += a0;
-                bsum[1] += a1;
-            }
+        for (int kp = 0; kp < 16; ++kp) {
+            const int k = 2 * kp + khalf;
+            const float a0 = As[cur][k][wi * 64 + lrow], a1 = As[cur][k][wi * 64 + 32 + lrow];
+            const float b0 = Bs[cur][k][wj * 64 + lrow], b1 = Bs[cur][k][wj * 64 + 32 + lrow];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            bsum[0] += a0;
+            bsum[1] += a1;
         }
         if (c + 1 < nchunks) swrite(cur ^ 1);
         __syncthreads();
@@ -764,15 +666,9 @@ int pack_tiles(const float* params, const rlx_mlp_layout& lay, float* tiles, hip
 }
 
 }  // namespace
-namespace step {
-long long* g_timing_buffer = nullptr;
-}
 }  // namespace rlx
 
 using namespace rlx;
-
-// development hook (not declared in include/rlx.h): device buffer of >= 32 int64 for the phase stamps, or NULL
-extern "C" void rlx_dev_set_timing_buffer(void* device_ptr) { g_timing_buffer = static_cast<long long*>(device_ptr); }
 
 extern "C" int rlx_mlp_rollout_step(const rlx_rollout_step* r, rlx_stream_t stream) {
     RLX_REQUIRE(r != nullptr, "rlx_mlp_rollout_step: NULL argument struct");
@@ -781,7 +677,6 @@ extern "C" int rlx_mlp_rollout_step(const rlx_rollout_step* r, rlx_stream_t stre
     RLX_REQUIRE(r->m >= 0 && r->n_value_jobs >= 0 && r->n_value_jobs <= 2, "rlx_mlp_rollout_step: bad sizes");
     RLX_REQUIRE(r->m == 0 || (r->states && r->action && r->logprob && r->value), "rlx_mlp_rollout_step: NULL policy tensor");
     RolloutArgs a{};
-    a.stamps = g_timing_buffer;
     a.params = r->params; a.tiles = r->tiles; a.lay = *r->layout; a.states = r->states; a.eps = r->eps; a.M = r->m;
     a.action = r->action; a.logprob = r->logprob; a.value = r->value; a.states_copy = r->states_copy;
     const int bm = 16;  // rows per workgroup
@@ -882,9 +777,6 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(s->workspace);
     StepArgs a{};
-    a.stamps = g_timing_buffer;
-    a.merged_loss_pass = 1;
-    a.xcd_rows = 0;  // measured: no effect (see the kernel), identity kept
     a.params = s->params; a.lay = lay; a.states = s->states; a.action = s->action; a.old_logprobs = s->old_logprobs;
     a.advantages = s->advantages; a.prev_values = s->prev_values; a.returns = s->returns; a.loss_mask = s->loss_mask;
     a.loss_mask_sum = s->loss_mask_sum; a.M = s->m; a.p = p; a.grad_out = s->grad_out;
@@ -897,12 +789,10 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
         a.dec.v_theta_dev = s->current_version_dev; a.dec.proximal = s->proximal_logprobs; a.dec.versions = s->versions;
     }
     DwArgs d{};
-    d.stamps = g_timing_buffer ? g_timing_buffer + 32 : nullptr;
     d.lay = lay; d.states = s->states; d.h = a.h; d.dz = a.dz; d.head_part = a.head_part; d.loss_part = a.loss_part;
     d.M = s->m; d.rows_per_slab = pl.rows_per_slab; d.slabs = pl.slabs; d.tiles = pl.loss_slots; d.head_parts = pl.head_parts;
     d.head_stride = pl.head_stride;
     d.gemm_items = pl.slabs * 20; d.grads = s->grads; d.p = p; d.has_mask = s->loss_mask != nullptr;
-    d.repeat = 1;
     d.has_msum = s->loss_mask_sum != nullptr; d.out = s->out;
     d.decoupled = dp != nullptr; d.dec_use_threshold = dp != nullptr && dp->use_behave_threshold != 0;
     const int dw_blocks = round_up(d.gemm_items, 8) + pl.slabs * 2 + 1;
@@ -935,29 +825,23 @@ extern "C" int rlx_ppo_step(const rlx_ppo_step_args* s, rlx_stream_t stream) {
     }
     const size_t lds = Geo<4, 8>::LDS_BYTES;
     const bool op8 = lay.act_dim <= 8 && lay.val_dim <= 8;
-#define RLX_LAUNCH_FUSED(PDV, ABLV, OPV)                                                                                  \
+#define RLX_LAUNCH_FUSED(OPV, DECV)                                                                                       \
     do {                                                                                                                  \
-        if (int rc = set_lds(ppo_step_fused_kernel<4, 8, PDV, ABLV, OPV>, lds)) return rc;                                \
-        hipLaunchKernelGGL((ppo_step_fused_kernel<4, 8, PDV, ABLV, OPV>), dim3(pl.tiles, 2), dim3(512), lds, st, a);      \
+        if (int rc = set_lds(ppo_step_fused_kernel<4, 8, 2, OPV, DECV>, lds)) return rc;                                  \
+        hipLaunchKernelGGL((ppo_step_fused_kernel<4, 8, 2, OPV, DECV>), dim3(pl.tiles, 2), dim3(512), lds, st, a);        \
     } while (0)
     if (a.dec.on) {
-        if (op8) {
-            if (int rc = set_lds(ppo_step_fused_kernel<4, 8, 2, 0, 8, true>, lds)) return rc;
-            hipLaunchKernelGGL((ppo_step_fused_kernel<4, 8, 2, 0, 8, true>), dim3(pl.tiles, 2), dim3(512), lds, st, a);
-        } else {
-            if (int rc = set_lds(ppo_step_fused_kernel<4, 8, 2, 0, 16, true>, lds)) return rc;
-            hipLaunchKernelGGL((ppo_step_fused_kernel<4, 8, 2, 0, 16, true>), dim3(pl.tiles, 2), dim3(512), lds, st, a);
-        }
+        if (op8) RLX_LAUNCH_FUSED(8, true);
+        else RLX_LAUNCH_FUSED(16, true);
     } else if (!op8) {
-        RLX_LAUNCH_FUSED(2, 0, 16);
+        RLX_LAUNCH_FUSED(16, false);
     } else {
-        RLX_LAUNCH_FUSED(2, 0, 8);
+        RLX_LAUNCH_FUSED(8, false);
     }
 #undef RLX_LAUNCH_FUSED
     RLX_LAUNCH_CHECK();
     const int blocks = dw_blocks;
-    // (reached with RLX_F32_EXACT_MFMA=1 only: exact f32 products on v_mfma_f32_32x32x2_f32)
-    hipLaunchKernelGGL(ppo_step_dw_kernel<false>, dim3(blocks), dim3(256), 0, st, d);
+    hipLaunchKernelGGL(ppo_step_dw_kernel, dim3(blocks), dim3(256), 0, st, d);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -31,10 +31,6 @@ struct GeoB {
     static constexpr int BIAS_OFF = MAX_OUT * W4S + MAX_OUT + 8 * BM * MAX_OUT;  // floats past the slab
     static constexpr int AUX_FLOATS = BIAS_OFF + 3 * HID + 4 * MAX_OUT;
     static constexpr size_t LDS_BYTES = (size_t)(SLAB_FLOATS + AUX_FLOATS) * sizeof(float) + 4096;
-    // fused step only: the rounded activations h1, h2 in the accumulator layout, one 8-byte word per lane and 16x16 tile
-    // (lane-linear: conflict-free b64 accesses), read back by the backward epilogues -- 32 VGPRs that no longer pin the kernel
-    // at the register limit (the spills they caused were reloaded with vmcnt(0) waits, i.e. behind the weight prefetch)
-    static constexpr size_t KEEP_BYTES = RT == 4 ? (size_t)2 * BM * HID * sizeof(__bf16) : 0;  // RT == 2: registers (16 VGPRs)
 };
 
 // bf16 weight tiles: same matrix list and element offsets as struct Tiles, tile = 16 (n) x 32 (k), K-STEP MAJOR:
@@ -64,14 +60,6 @@ __global__ __launch_bounds__(256) void pack_tiles_bf16_kernel(const float* __res
         else v = params[lay.off_w[y][m - 2] + (size_t)k * HID + n];
         tiles[i] = (__bf16)v;
     }
-}
-
-template <int RT, int CT>
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[RT][CT]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // acc = Xb[0:BM, 0:32*nit] . W^T, weights as bf16 fragment tiles streamed L2 -> registers (ring of PD stages), the A operand
@@ -242,11 +230,11 @@ struct StatesB {
     }
 };
 
-// forward hidden-layer epilogue: h = bf16(tanh(acc + bias)) -> slab; KEEP: the rounded value also goes to `kept` (registers) or
-// `keep_lds` (lane-linear LDS words) for the backward sweep's 1 - h^2, and to the k-tiled image `dst`.  `bias` is an LDS image.
+// forward hidden-layer epilogue: h = bf16(tanh(acc + bias)) -> slab; KEEP: the rounded value also goes to `kept` (registers) for the
+// backward sweep's 1 - h^2, and to the k-tiled image `dst`.  `bias` is an LDS image.
 template <int RT, int NW, bool KEEP>
 __device__ __forceinline__ void epilogue_tanh_b(const f32x4 (&acc)[RT][GeoB<RT, NW>::CT], const float* bias, __bf16* Xb,
-                                                bf16x4 (*kept)[GeoB<RT, NW>::CT], bf16x4* keep_lds, __bf16* __restrict__ dst, int nrb,
+                                                bf16x4 (*kept)[GeoB<RT, NW>::CT], __bf16* __restrict__ dst, int nrb,
                                                 long long m0) {
     typedef GeoB<RT, NW> G;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r16 = lane & 15;
@@ -274,10 +262,8 @@ __device__ __forceinline__ void epilogue_tanh_b(const f32x4 (&acc)[RT][GeoB<RT, 
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-            for (int ct = 0; ct < G::CT; ++ct) {
-                if (keep_lds != nullptr) keep_lds[(rt * G::CT + ct) * G::NT + threadIdx.x] = hloc[rt][ct];
+            for (int ct = 0; ct < G::CT; ++ct)
                 if (kept != nullptr) kept[rt][ct] = hloc[rt][ct];
-            }
     }
     lds_barrier();
 }
@@ -285,7 +271,7 @@ __device__ __forceinline__ void epilogue_tanh_b(const f32x4 (&acc)[RT][GeoB<RT, 
 
 // head forward: out[row][o] = h3[row][:] . W4[o][:], written as TWO k-half partials P0 / P1 [BM][MAX_OUT] (the caller adds them
 // and the bias: P0 + P1 + b).  Wave w < 2 RT takes row tile w % RT and k half w / RT -- the rollout launch (RT = 1) and the
-// training launch (RT = 4) therefore add every row's products in the same order: the log-prob a sample gets at rollout time
+// training launch (RT = 2) therefore add every row's products in the same order: the log-prob a sample gets at rollout time
 // and the one the first training epoch recomputes are bit-identical, as with the reference.  Rows of W4s past n_out are zero.
 template <int RT>
 __device__ __forceinline__ void head_forward_mfma(const __bf16* Xb, const float* W4s, float* P0, float* P1) {
@@ -309,9 +295,8 @@ __device__ __forceinline__ void head_forward_mfma(const __bf16* Xb, const float*
 // ---------------------------------------------------------------------------------------------------------------
 // rollout step (RT = 1, NW = 8)
 // ---------------------------------------------------------------------------------------------------------------
-template <int RT, int ORDER = 1345>  // 16 RT rows per workgroup; ORDER: where the weight fragments of layers 2 and 3 are requested
 __global__ __launch_bounds__(512) void rollout_step_bf16_kernel(RolloutArgs a) {
-    constexpr int NW = 8;
+    constexpr int RT = 1, NW = 8;
     touch_kernargs<(int)sizeof(RolloutArgs)>();
     typedef GeoB<RT, NW> G;
     extern __shared__ __align__(16) float smem[];
@@ -358,38 +343,29 @@ __global__ __launch_bounds__(512) void rollout_step_bf16_kernel(RolloutArgs a) {
     // WHEN the weight fragments are requested decides this launch.  A workgroup's 288 KB of fragments pass the CU's address
     // unit at 64 B / clk: 4.6 k cycles, and a wave that issues loads faster than that STALLS in issue -- with everything requested
     // up front (rounds 3-5: "one memory round trip per launch") the waves spent 3.9 k cycles issuing and the first barrier fell at
-    // 7.8 k of the launch's 13.7 k (phase stamps, development build), the products and epilogues (5.9 k) queueing behind it.
+    // 7.8 k of the launch's 13.7 k (phase stamps), the products and epilogues (5.9 k) queueing behind it.
     // Requested one phase ahead of their use, half a layer at a time, the same bytes stream while the earlier layers compute.
-    // ORDER = four decimal digits (W2 first half, W2 second half, W3 first half, W3 second half): the point at which that half
-    // layer is requested -- 0 up front, 1 behind the commits, 2 behind the first barrier, 3 behind the first layer's products,
-    // 4 behind its epilogue, 5 behind the second layer's products.  Same loads, same arithmetic: bit-identical outputs.
-    constexpr int P2A = ORDER / 1000 % 10, P2B = ORDER / 100 % 10, P3A = ORDER / 10 % 10, P3B = ORDER % 10, H = HID / 64;
-#define RLX_POINT(N)                                                                               \
-    {                                                                                              \
-        if constexpr (P2A == N) gemm2.template prefetch_part<0, H>(tiles + Tiles::mat(y, 1), HID / 32);      \
-        if constexpr (P2B == N) gemm2.template prefetch_part<H, 2 * H>(tiles + Tiles::mat(y, 1), HID / 32);  \
-        if constexpr (P3A == N) gemm3.template prefetch_part<0, H>(tiles + Tiles::mat(y, 2), HID / 32);      \
-        if constexpr (P3B == N) gemm3.template prefetch_part<H, 2 * H>(tiles + Tiles::mat(y, 2), HID / 32);  \
-    }
+    // W2's first half goes behind the commits, its second half behind the first layer's products, W3's halves behind the first
+    // layer's epilogue and the second layer's products: 6.84 us in a replayed graph of 64 steps against 7.84 with everything up
+    // front, best of 25 request orders (profiles/r06_rollout_request_order.txt, "ORDER 1345").  Same loads, same arithmetic:
+    // bit-identical outputs.
+    constexpr int H = HID / 64;  // k-steps of half a layer
     gemm1.prefetch(tiles + Tiles::mat(y, 0), Tiles::K1P / 32);
-    RLX_POINT(0)
     st.commit(states, states_copy, D, m0, M, Xb);
     si.commit(n_out, sBias, W4s, b4s, sStd);
     for (int i = n_out * W4S + tid; i < MAX_OUT * W4S; i += G::NT) W4s[i] = 0.f;
-    RLX_POINT(1)
+    gemm2.prefetch_part<0, H>(tiles + Tiles::mat(y, 1), HID / 32);
     lds_barrier();
-    RLX_POINT(2)
     f32x4 acc[RT][G::CT];
     gemm1.run(Xb, acc);
-    RLX_POINT(3)
-    epilogue_tanh_b<RT, NW, false>(acc, sBias, Xb, nullptr, nullptr, nullptr, 0, m0);
-    RLX_POINT(4)
+    gemm2.prefetch_part<H, 2 * H>(tiles + Tiles::mat(y, 1), HID / 32);
+    epilogue_tanh_b<RT, NW, false>(acc, sBias, Xb, nullptr, nullptr, 0, m0);
+    gemm3.prefetch_part<0, H>(tiles + Tiles::mat(y, 2), HID / 32);
     gemm2.run(Xb, acc);
-    RLX_POINT(5)
-#undef RLX_POINT
-    epilogue_tanh_b<RT, NW, false>(acc, sBias + HID, Xb, nullptr, nullptr, nullptr, 0, m0);
+    gemm3.prefetch_part<H, 2 * H>(tiles + Tiles::mat(y, 2), HID / 32);
+    epilogue_tanh_b<RT, NW, false>(acc, sBias + HID, Xb, nullptr, nullptr, 0, m0);
     gemm3.run(Xb, acc);
-    epilogue_tanh_b<RT, NW, false>(acc, sBias + 2 * HID, Xb, nullptr, nullptr, nullptr, 0, m0);
+    epilogue_tanh_b<RT, NW, false>(acc, sBias + 2 * HID, Xb, nullptr, nullptr, 0, m0);
 
     static_assert(G::BM * MAX_OUT <= G::NT, "one head output per lane");
     float* sP0 = b4s + MAX_OUT, *sP1 = sP0 + G::BM * MAX_OUT;
@@ -421,8 +397,12 @@ __global__ __launch_bounds__(512) void rollout_step_bf16_kernel(RolloutArgs a) {
 //   h  : [2 nets][2][16 cb][nrb] tiles    dz : [2 nets][3][16 cb][nrb] tiles    st : [4 cb][nrb] tiles (states)
 // ---------------------------------------------------------------------------------------------------------------
 
-template <int RT, int NW, int PD, int OP, bool STAMPS, bool DEC = false>  // DEC: the decoupled actor loss (StepArgs.dec)
-__global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_kernel(StepArgs a, __bf16* st_tiles) {
+// 32 rows per workgroup (two workgroups per CU at 8192 rows, 58 KB of LDS and 128 VGPRs each: 25.6 us against 27.7 us for 64-row
+// tiles, profiles/r02_fused_rows_per_workgroup.txt; see plan_step), weight ring of 4 stages.
+constexpr int FUSED_RT = 2, FUSED_PD = 4;
+template <bool DEC>  // DEC: the decoupled actor loss (StepArgs.dec)
+__global__ __launch_bounds__(512, 4) void ppo_step_fused_bf16_kernel(StepArgs a, __bf16* st_tiles) {
+    constexpr int RT = FUSED_RT, NW = 8, PD = FUSED_PD;
     typedef GeoB<RT, NW> G;
     constexpr int BM = G::BM, CT = G::CT;
     extern __shared__ __align__(16) float smem[];
@@ -441,19 +421,12 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
     float* sRet = sAdv + BM * MAX_OUT;
     double* sRed = reinterpret_cast<double*>(smem + G::SLAB_FLOATS + G::AUX_FLOATS);
     double* sNm = sRed + 256;
-    bf16x4* sKeep = reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(smem) + G::LDS_BYTES);  // [2][RT * CT][NT] words
 
     const rlx_mlp_layout& lay = a.lay;
     const rlx_ppo_loss_params& p = a.p;
-    // Workgroups go to the 8 XCDs round-robin (linear id % 8 = blockIdx.x % 8: gridDim.x is a multiple of 8 whenever the remap is
-    // used).  The weight-gradient launch behind this one gives XCD x the split-K slabs over rows [x M / 8, (x + 1) M / 8); with the
-    // identity map those rows were written by ALL XCDs and every operand fetch of that launch is a memory-side trip.  Remapped
-    // (StepArgs.xcd_rows = 1), XCD x writes exactly the rows it reads back next -- measured, same box, 3200 launches
-    // each: weight-gradient launch 15.88 -> 15.64 us, this launch 25.16 -> 25.44 us (profiles/r03_xcd_row_map_*.txt).  A launch
-    // boundary writes back AND invalidates the XCD's L2, so which XCD produced a line does not matter to the next launch; only
-    // producer and consumer inside ONE launch could share an L2.  The identity map stays.
-    const int nt = gridDim.x, bx = blockIdx.x;
-    const int y = blockIdx.y, tile = (a.xcd_rows && (nt & 7) == 0) ? (bx & 7) * (nt >> 3) + (bx >> 3) : bx, D = lay.obs_dim, tid = threadIdx.x;
+    // (A workgroup -> row-tile map that makes every XCD write the rows the weight-gradient launch reads back on the same XCD was
+    //  measured and bought nothing -- a launch boundary writes back and invalidates the L2s: profiles/r03_xcd_row_map_*.txt.)
+    const int y = blockIdx.y, tile = blockIdx.x, D = lay.obs_dim, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, r16 = lane & 15, kq = lane >> 4;
     const long long m0 = (long long)tile * BM, M = a.M;
     const int n_out = y == 1 ? lay.act_dim : lay.val_dim;
@@ -473,8 +446,6 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
     }
 
     // ---- forward -----------------------------------------------------------------------------------------------------
-    StampsT<STAMPS> ts{a.stamps, 0};  // development: phase stamps of block (0, 0), see tools/phase_times.py
-    ts.mark();
     float* sBias = smem + G::SLAB_FLOATS + G::BIAS_OFF;
     float* sStd = sBias + 3 * HID;
     // Request order = wait order (a wave's loads retire in order): the tile's states first, then the loss inputs, the biases /
@@ -505,9 +476,7 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
     __builtin_amdgcn_sched_barrier(0);
     RowGemmB<RT, NW, PD> gemm;
     gemm.prefetch(tiles + Tiles::mat(y, 0), Tiles::K1P / 32);
-    ts.mark();  // (every input requested)
     st.commit(a.states, nullptr, D, m0, M, Xb);
-    ts.mark();
 #pragma unroll
     for (int u = 0; u < PI; ++u) {
         const int i = tid + u * G::NT;
@@ -525,32 +494,21 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
     for (int i = n_out * W4S + tid; i < MAX_OUT * W4S; i += G::NT) W4s[i] = 0.f;
     lds_barrier();
     if (y == 1) StatesB<RT, NW>::tiles(st_tiles, tg.nrb, D, m0, Xb);
-    ts.mark();
     f32x4 acc[RT][CT];
-    bf16x4 kept3[RT][CT];  // rounded h3 in the accumulator layout (h1, h2: sKeep): the backward epilogues need exactly these lanes
-    constexpr bool KEEP_LDS = RT == 4;
-    bf16x4 kept12[KEEP_LDS ? 1 : 2][RT][CT];  // the 32-row variant has the registers for h1, h2 as well
+    bf16x4 kept3[RT][CT], kept12[2][RT][CT];  // rounded h3, h1, h2 in the accumulator layout: the backward epilogues need exactly these lanes
     gemm.run(Xb, acc);
     gemm.prefetch(tiles + Tiles::mat(y, 1), HID / 32);
-    ts.mark();
-    epilogue_tanh_b<RT, NW, true>(acc, sBias, Xb, KEEP_LDS ? nullptr : kept12[0], KEEP_LDS ? sKeep : nullptr, hy, tg.nrb, m0);
-    ts.mark();
+    epilogue_tanh_b<RT, NW, true>(acc, sBias, Xb, kept12[0], hy, tg.nrb, m0);
     gemm.run(Xb, acc);
     gemm.prefetch(tiles + Tiles::mat(y, 2), HID / 32);
-    ts.mark();
-    epilogue_tanh_b<RT, NW, true>(acc, sBias + HID, Xb, KEEP_LDS ? nullptr : kept12[KEEP_LDS ? 0 : 1], KEEP_LDS ? sKeep + RT * CT * G::NT : nullptr,
-                                  hy + tg.mat(), tg.nrb, m0);
-    ts.mark();
+    epilogue_tanh_b<RT, NW, true>(acc, sBias + HID, Xb, kept12[1], hy + tg.mat(), tg.nrb, m0);
     gemm.run(Xb, acc);
-    ts.mark();
-    epilogue_tanh_b<RT, NW, true>(acc, sBias + 2 * HID, Xb, kept3, nullptr, nullptr, tg.nrb, m0);
-    ts.mark();
+    epilogue_tanh_b<RT, NW, true>(acc, sBias + 2 * HID, Xb, kept3, nullptr, tg.nrb, m0);
 
     // ---- head + loss element math (f32, identical to ppo_step.hip): fused_loss_pass, ppo_step_bf16_parts.h -------------------------
     head_forward_mfma<RT>(Xb, W4s, sG, sLp);  // the two k-half partials land in sG / sLp (both free until the passes below)
     lds_barrier();
-    ts.mark();
-    fused_loss_pass<BM, NW, DEC>(a, y, tile, m0, LossLds{b4s, sHead, sLp, sG, sD, sOld, sAct, sAdv, sRet, sStd, reinterpret_cast<double*>(Xb), sNm}, ts);
+    fused_loss_pass<BM, NW, DEC>(a, y, tile, m0, LossLds{b4s, sHead, sLp, sG, sD, sOld, sAct, sAdv, sRet, sStd, reinterpret_cast<double*>(Xb), sNm});
     // ---- head parameter gradients per 32-row half tile: dW4[o][j] = sum_rows dOut[row][o] h3[row][j] on the matrix pipe -------
     // M = o, N = j (this wave's 2 x 16 columns), K = the half's 32 rows.  K is only a summation index, so the k slots are
     // mapped to rows the way the accumulator layout already holds h3: lane (r16, kq) slot jj <-> row (jj >> 2) * 16 + 4 kq +
@@ -598,7 +556,6 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
         }
     }
 
-    ts.mark();
     // ---- dZ3 = (dOut . W4) * (1 - h3^2) -> bf16 slab + tiles: K = n_out is tiny, f32 operands -> v_mfma_f32_16x16x4_f32 ------
     gemm.prefetch(tiles + Tiles::mat(y, 4), HID / 32);  // W3^T
     bf16x4 dv[RT][CT];
@@ -631,7 +588,6 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
             store_slab_quad(Xb, rt * 16, wave * 16 * CT + ct * 16, dv[rt][ct]);
     store_tiles<RT, NW>(dv, dzy + 2 * tg.mat(), tg.nrb, m0);
     lds_barrier();
-    ts.mark();
 
     // ---- backward-data chain ---------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -642,20 +598,13 @@ __global__ __launch_bounds__(64 * NW, RT == 2 ? 4 : 2) void ppo_step_fused_bf16_
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                const bf16x4 hk = KEEP_LDS ? sKeep[((l - 1) * RT * CT + rt * CT + ct) * G::NT + tid] : kept12[KEEP_LDS ? 0 : l - 1][rt][ct];
+                const bf16x4 hk = kept12[l - 1][rt][ct];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dv[rt][ct][r] = (__bf16)(acc[rt][ct][r] * dtanh_b(hk[r]));
                 if (l == 2) store_slab_quad(Xb, rt * 16, wave * 16 * CT + ct * 16, dv[rt][ct]);
             }
         store_tiles<RT, NW>(dv, dzy + (size_t)(l - 1) * tg.mat(), tg.nrb, m0);
         if (l == 2) lds_barrier();
-        ts.mark();
-    }
-    if constexpr (STAMPS) {
-        if (a.stamps != nullptr && blockIdx.x == 0 && blockIdx.y == 1 && threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            a.stamps[ts.n] = (long long)clock64();  // ... and the stores have drained
-        }
     }
 }
 
@@ -700,7 +649,7 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
     const int gemm_blocks = round_up(a.gemm_items, 8);
     int b = blockIdx.x;
 
-    if (b >= gemm_blocks) {
+    if (b >= gemm_blocks) {  // (not dw_tail_block<256>: through it hipcc allocates this kernel's scalar registers differently)
         b -= gemm_blocks;
         if (b < a.slabs * 2) {
             head_reduce_block(a, b >> 1, b & 1, tid);
@@ -712,14 +661,8 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
     }
     const int item = (b & 7) * (gemm_blocks >> 3) + (b >> 3);
     if (item >= a.gemm_items) return;
-    const int s = item / 20, w = item % 20;
-    int y, l, i0, j0;
-    if (w < 16) {
-        const int mat = w >> 2, tile = w & 3;
-        y = mat >> 1; l = 1 + (mat & 1); i0 = (tile >> 1) * 128; j0 = (tile & 1) * 128;
-    } else {
-        y = (w - 16) >> 1; l = 0; i0 = ((w - 16) & 1) * 128; j0 = 0;
-    }
+    const DwItem it = dw_item(item);
+    const int s = it.s, y = it.y, l = it.l, i0 = it.i0, j0 = it.j0;
     const int nrb = (int)((M + 31) / 32);
     const size_t mat_elems = (size_t)16 * nrb * 512;
     const int Kin = l == 0 ? lay.obs_dim : HID;
@@ -756,12 +699,7 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
     float bsum[4] = {0.f, 0.f, 0.f, 0.f};
     const bool live = j0 + wj * 64 < Kin;  // first layers: only the first 64-column block holds inputs (the wave still copies)
 
-    // stamps by the workgroup that owns GEMM item 0
-    long long* stp = (a.stamps != nullptr && item == 0 && tid == 0) ? a.stamps : nullptr;
-    if (stp) stp[0] = clock64();
     constexpr int AHEAD = DW_NBUF - 1;  // k-blocks in flight
-    for (int rep = 0; rep < a.repeat; ++rep) {  // (DwArgs.repeat is always 1)
-    if (rep > 0) __builtin_amdgcn_s_barrier();  // everybody finished reading the last k-blocks before the ring is refilled
 #pragma unroll
     for (int d = 0; d < AHEAD; ++d)
         if (d < nkb) dma(d, d);
@@ -770,7 +708,6 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
         wait_copies_ahead<AHEAD - 1>(min(AHEAD - 1, nkb - 1 - kb));
         __builtin_amdgcn_s_barrier();  // everybody's copies of kb landed; everybody finished reading kb - 1
         asm volatile("" ::: "memory");
-        if (stp && kb < 12) stp[1 + kb] = clock64();
         if (kb + AHEAD < nkb) dma(kb + AHEAD, (kb + AHEAD) % DW_NBUF);  // into the buffer k-block kb - 1 just vacated
         const char* buf = dsm + (kb % DW_NBUF) * DW_BUF_BYTES + lane * 16;
         bf16x8 fa[4], fb[4];
@@ -793,8 +730,6 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the fragment reads are done before this wave arrives at the next barrier
     }
-    }
-    if (stp) stp[14] = clock64();
     if (!live) return;
     float* slab = a.grads + (size_t)s * lay.n_params;
     float* dW = slab + lay.off_w[y][l];
@@ -819,10 +754,6 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
             tot += __shfl_xor(tot, 32, 64);
             if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
         }
-    }
-    if (stp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stp[15] = clock64();
     }
 }
 
@@ -852,12 +783,6 @@ __device__ __forceinline__ void dwr_wait_behind(int behind) {  // vmcnt(8 x behi
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 }
-__device__ __forceinline__ void dwr_barrier() {  // lgkmcnt(0) as the builtin: hipcc then knows the fragment reads have landed
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 template <int DW_NBUF>
 __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwArgs a, const __bf16* __restrict__ st_tiles) {
@@ -867,28 +792,16 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
     const long long M = a.M;
     const int tid = threadIdx.x;
     const int gemm_blocks = round_up(a.gemm_items, 8);
-    int b = blockIdx.x;
+    const int b = blockIdx.x;
 
     if (b >= gemm_blocks) {
-        b -= gemm_blocks;
-        if (b < a.slabs * 2) {
-            if (tid < 256) head_reduce_block(a, b >> 1, b & 1, tid);
-        } else {
-            double* s_red = reinterpret_cast<double*>(dsm);
-            metric_block(a, s_red, tid, DWR_THREADS);
-        }
+        dw_tail_block<DWR_THREADS>(a, b - gemm_blocks, dsm, tid);
         return;
     }
     const int item = (b & 7) * (gemm_blocks >> 3) + (b >> 3);
     if (item >= a.gemm_items) return;
-    const int s = item / 20, w = item % 20;
-    int y, l, i0, j0;
-    if (w < 16) {
-        const int mat = w >> 2, tile = w & 3;
-        y = mat >> 1; l = 1 + (mat & 1); i0 = (tile >> 1) * 128; j0 = (tile & 1) * 128;
-    } else {
-        y = (w - 16) >> 1; l = 0; i0 = ((w - 16) & 1) * 128; j0 = 0;
-    }
+    const DwItem it = dw_item(item);
+    const int s = it.s, y = it.y, l = it.l, i0 = it.i0, j0 = it.j0;
     const int nrb = (int)((M + 31) / 32);
     const size_t mat_elems = (size_t)16 * nrb * 512;
     const int Kin = l == 0 ? lay.obs_dim : HID;
@@ -939,8 +852,6 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    long long* stp = (a.stamps != nullptr && item == 0 && tid == 0) ? a.stamps : nullptr;
-    if (stp) stp[0] = clock64();
     bf16x8 fa[2][4], fb[2][4];
     auto read_frags = [&](int kb, bf16x8 (&xa)[4], bf16x8 (&xb)[4]) {
         const char* buf = dsm + (kb % DW_NBUF) * DW_BUF_BYTES + lane * 16;
@@ -975,7 +886,6 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
             __builtin_amdgcn_sched_barrier(0);
             if (kb + 1 < nkb) {
                 dwr_barrier();  // hand-off kb + 1
-                if (stp && kb < 12) stp[1 + kb] = clock64();
                 read_frags(kb + 1, fa[d ^ 1], fb[d ^ 1]);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -983,7 +893,6 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    if (stp) stp[14] = clock64();
     dwr_barrier();  // every compute wave has read its last fragments (the loaders are gone): the ring becomes the store staging area
     float* slab = a.grads + (size_t)s * lay.n_params;
     float* dW = slab + lay.off_w[y][l];
@@ -1036,10 +945,6 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
             if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
         }
     }
-    if (stp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stp[15] = clock64();
-    }
 }
 
 }  // namespace
@@ -1054,10 +959,8 @@ int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles,
 
 int launch_rollout_bf16(const RolloutArgs& a, int blocks, hipStream_t st) {
     const size_t lds = GeoB<1, 8>::LDS_BYTES;
-    // Half layers requested one phase ahead of their use (ORDER 1345, see the kernel): measured in a replayed graph of 64 steps,
-    // 7.84 -> 6.84 us against everything up front (ORDER 0); profiles/r06_rollout_request_order.txt.
-    if (int rc = set_lds(rollout_step_bf16_kernel<1, 1345>, lds)) return rc;
-    hipLaunchKernelGGL((rollout_step_bf16_kernel<1, 1345>), dim3(blocks), dim3(512), lds, st, a);
+    if (int rc = set_lds(rollout_step_bf16_kernel, lds)) return rc;
+    hipLaunchKernelGGL(rollout_step_bf16_kernel, dim3(blocks), dim3(512), lds, st, a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
@@ -1067,17 +970,14 @@ size_t bf16_image_bytes(int64_t m) { return (size_t)16 * ((m + 31) / 32) * 512 *
 
 int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st) {
     __bf16* stt = static_cast<__bf16*>(st_tiles);
-#define RLX_FUSED_LAUNCH(RTV, PDV, OPV, STV, DECV, LDSB)                                                                              \
-    {                                                                                                                              \
-        const size_t lb = (LDSB);                                                                                                  \
-        if (int rc = set_lds(ppo_step_fused_bf16_kernel<RTV, 8, PDV, OPV, STV, DECV>, lb)) return rc;                            \
-        hipLaunchKernelGGL((ppo_step_fused_bf16_kernel<RTV, 8, PDV, OPV, STV, DECV>), dim3(tiles, 2), dim3(512), lb, st, a, stt); \
+    const size_t lds = GeoB<FUSED_RT, 8>::LDS_BYTES;
+    if (a.dec.on) {
+        if (int rc = set_lds(ppo_step_fused_bf16_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(ppo_step_fused_bf16_kernel<true>, dim3(tiles, 2), dim3(512), lds, st, a, stt);
+    } else {
+        if (int rc = set_lds(ppo_step_fused_bf16_kernel<false>, lds)) return rc;
+        hipLaunchKernelGGL(ppo_step_fused_bf16_kernel<false>, dim3(tiles, 2), dim3(512), lds, st, a, stt);
     }
-    const size_t lds32 = GeoB<2, 8>::LDS_BYTES;
-    // 32-row tiles (two workgroups per CU), weight ring of 4 stages; its decoupled-loss instantiation
-    if (a.dec.on) RLX_FUSED_LAUNCH(2, 4, 8, false, true, lds32)
-    else RLX_FUSED_LAUNCH(2, 4, 8, false, false, lds32)
-#undef RLX_FUSED_LAUNCH
     RLX_LAUNCH_CHECK();
 #define RLX_DWR_LAUNCH(NB)                                                                                                         \
     {                                                                                                                              \

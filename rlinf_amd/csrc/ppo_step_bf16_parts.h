@@ -102,20 +102,6 @@ struct TileGeom {
     __host__ __device__ size_t mat() const { return (size_t)16 * nrb * 512; }  // elements per [M][256] image
 };
 
-// STAMPS: the development build of the same kernel with phase stamps (tools/phase_times.py); reading the cycle counter orders
-// the surrounding memory operations (+5 us measured), so the product instantiation carries none.
-template <bool ON>
-struct StampsT {
-    long long* buf;
-    int n;
-    __device__ __forceinline__ void mark() {
-        if constexpr (ON) {
-            if (buf != nullptr && blockIdx.x == 0 && blockIdx.y == 1 && threadIdx.x == 0) buf[n] = (long long)clock64();  // the policy network's tile 0
-            ++n;
-        }
-    }
-};
-
 // The small parameter inputs of a tile: the three hidden layers' biases, the f32 head image + bias, the policy's log-std.
 // issue() requests them into registers (clamped, unconditional), commit() writes them to LDS: sBias [3][HID], W4s / b4s, and
 // sStd = std | var | log(std) per output (the same expf / fmul / logf the per-element code used to repeat).
@@ -235,8 +221,8 @@ struct LossLds {
     double* sLacc;
     const double* sNm;
 };
-template <int BM, int NW, bool DEC, typename TS>
-__device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int tile, long long m0, const LossLds& L, TS& ts) {
+template <int BM, int NW, bool DEC>
+__device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int tile, long long m0, const LossLds& L) {
     constexpr int OP = MAX_OUT;  // bound of the unrolled row sums
     constexpr int NT = 64 * NW;
     const rlx_mlp_layout& lay = a.lay;
@@ -268,7 +254,7 @@ __device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int ti
     // lane shifts and adds them in the reference's order (j ascending, starting from 0.f), evaluates the loss element and hands
     // d(loss)/d(logprob) back to its lanes.  Slot r of the metric partials is row r's element, exactly what wave 0's lane r
     // held in the general path: the butterfly sums -- and so the metrics -- are bit-identical between the two paths.
-    const bool fast = a.merged_loss_pass && BM * n_out <= NT && (y == 0 ? BM * n_out <= 64 : (npr == 1 && S == 1 && 64 % n_out == 0));
+    const bool fast = BM * n_out <= NT && (y == 0 ? BM * n_out <= 64 : (npr == 1 && S == 1 && 64 % n_out == 0));
     if (fast) {
         for (int i = tid; i < NS * 64; i += NT)
             if ((i & 63) >= (y == 0 ? BM * n_out : BM)) sLacc[i] = 0.0;  // the slots no element owns
@@ -333,8 +319,6 @@ __device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int ti
             for (int k = 0; k < NS; ++k) sLacc[k * 64 + tid] = lacc[k];
         }
         lds_barrier();
-        ts.mark();
-        ts.mark();  // (the general path's two intermediate stamps)
     } else {
         for (int idx = tid; idx < BM * n_out; idx += NT) {
             const int row = idx / n_out, o = idx % n_out;
@@ -350,7 +334,6 @@ __device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int ti
             }
         }
         lds_barrier();
-        ts.mark();
         // wave 0 walks the tile's loss elements (a fixed lane <-> element assignment keeps the f64 metric sums reproducible) and
         // parks its 16 per-lane partial sums in the slab (h3 is dead: the head gradients and dZ3 work from registers and sHead);
         // behind the barrier every wave butterfly-sums two of the 16 slots while all lanes run the dOut pass -- the same 64-lane
@@ -406,7 +389,6 @@ __device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int ti
             for (int k = 0; k < NS; ++k) sLacc[k * 64 + lane] = lacc[k];
         }
         lds_barrier();
-        ts.mark();
         if (y == 1) {
             for (int idx = tid; idx < BM * n_out; idx += NT) {
                 const int row = idx / n_out, o = idx % n_out;
@@ -430,7 +412,51 @@ __device__ __forceinline__ void fused_loss_pass(const StepArgs& a, int y, int ti
         }
     }
     lds_barrier();
-    ts.mark();
+}
+
+// accumulator tiles of a row GEMM (RowGemmB / RowGemmX and the fused kernels' dZ3 product)
+template <int RT, int CT>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[RT][CT]) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// ---- pieces of the weight-gradient launches (ppo_step_bf16.hip, ppo_step_f32x.hip) that do not depend on the number of operand
+// planes -----------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dwr_barrier() {  // lgkmcnt(0) as the builtin: hipcc then knows the fragment reads have landed
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// GEMM item -> (slab, network, layer, 128 x 128 output tile): 20 items per slab, 0-15 the hidden matrices (4 tiles each), 16-19 the
+// first layers (2 tiles each)
+struct DwItem {
+    int s, y, l, i0, j0;
+};
+__device__ __forceinline__ DwItem dw_item(int item) {
+    const int s = item / 20, w = item % 20;
+    int y, l, i0, j0;
+    if (w < 16) {
+        const int mat = w >> 2, tile = w & 3;
+        y = mat >> 1; l = 1 + (mat & 1); i0 = (tile >> 1) * 128; j0 = (tile & 1) * 128;
+    } else {
+        y = (w - 16) >> 1; l = 0; i0 = ((w - 16) & 1) * 128; j0 = 0;
+    }
+    return DwItem{s, y, l, i0, j0};
+}
+
+// the blocks behind the GEMM items: slabs x 2 head-gradient blocks (256 of the block's NT threads work), then the metric block
+template <int NT>
+__device__ __forceinline__ void dw_tail_block(const DwArgs& a, int b, char* dsm, int tid) {
+    if (b < a.slabs * 2) {
+        if (tid < 256) head_reduce_block(a, b >> 1, b & 1, tid);
+    } else {
+        metric_block(a, reinterpret_cast<double*>(dsm), tid, NT);
+    }
 }
 
 }  // namespace b16

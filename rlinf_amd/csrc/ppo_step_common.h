@@ -64,19 +64,6 @@ struct Tiles {
     }
 };
 
-// Phase stamps (development only): block 0 / thread 0 writes the shader clock at phase boundaries into a buffer set
-// with rlx_dev_set_timing_buffer(); the product never sets one.
-struct Stamps {
-    long long* buf;
-    int n;
-    __device__ __forceinline__ void mark() {
-        if (buf != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) buf[n] = (long long)clock64();
-        ++n;
-    }
-};
-// Ablation switches of the exact-f32 fused kernel's ABL parameter (measurement only: the launches instantiate ABL == 0)
-constexpr int ABL_NO_TANH = 1, ABL_NO_FLUSH = 2, ABL_NO_WLOAD = 4, ABL_NO_MFMA = 8;
-
 // stage the head weight [n_out][256] (+ bias) into LDS with a padded row stride
 __device__ __forceinline__ void stage_head(const float* __restrict__ W4, const float* __restrict__ b4, int n_out, float* W4s,
                                            float* b4s, int nthreads) {
@@ -149,7 +136,6 @@ __device__ __forceinline__ void value_job_output(const ValueJob& v, size_t g, si
     }
 }
 struct RolloutArgs {
-    long long* stamps;
     const float* params;
     const float* tiles;
     rlx_mlp_layout lay;
@@ -183,7 +169,6 @@ __device__ __forceinline__ loss::DecoupledMode decoupled_mode_now(const Decouple
 #endif
 
 struct StepArgs {
-    long long* stamps;
     const float* params;
     const float* tiles;         // fragment-tile weight image (struct Tiles), built by pack_tiles_kernel just before
     rlx_mlp_layout lay;
@@ -198,8 +183,6 @@ struct StepArgs {
     long long M;
     rlx_ppo_loss_params p;
     float grad_out;             // d(total)/d(loss) of this micro-batch (1 / gradient_accumulation)
-    int merged_loss_pass;       // bf16 launch: element math + loss element + dOut in one pass where the shapes allow (always 1)
-    int xcd_rows;               // bf16 launch: workgroup -> row-tile map that gives every XCD one CONTIGUOUS eighth of the rows (see the kernel)
     float* h;                   // [2 nets][2][M][256]  hidden activations 1, 2   (B operands of the weight gradients)
     float* dz;                  // [2 nets][3][M][256]  pre-activation gradients  (A operands)
     float* head_part;           // [head_parts][2][head_stride]  per-32-row head gradients: dW4 [n_out][256], db4, dlogstd [n_out]
@@ -209,7 +192,6 @@ struct StepArgs {
 };
 
 struct DwArgs {
-    long long* stamps;
     rlx_mlp_layout lay;
     const float* states;
     const float* h;          // [2][2][M][256]
@@ -223,7 +205,6 @@ struct DwArgs {
     int head_parts;          // head-gradient partial slots per network
     int head_stride;
     int gemm_items;          // slabs * 20, the grid holds round_up(gemm_items, 8) GEMM blocks
-    int repeat;              // always 1 (kept so that the argument offsets stay put): the bf16 LDS-DMA kernel walks its k-blocks `repeat` times
     float* grads;            // [slabs][n_params]
     rlx_ppo_loss_params p;
     int has_mask, has_msum;
@@ -425,8 +406,6 @@ inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = fals
     pl.bytes = off;
     return pl;
 }
-
-extern long long* g_timing_buffer;  // development: phase stamps (rlx_dev_set_timing_buffer)
 
 // bf16 launches (ppo_step_bf16.hip)
 int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);

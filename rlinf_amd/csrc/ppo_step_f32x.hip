@@ -69,15 +69,15 @@ __device__ __forceinline__ Quad3 split_quad(const float (&v)[4]) {
 // spent most of its k-step on.  The order per accumulator is unchanged by the interleaving: bit-identical sums.
 __device__ constexpr int PA(int q) { return q == 0 ? 2 : (q == 2 || q == 3) ? 1 : 0; }
 __device__ constexpr int PB(int q) { return q == 1 ? 2 : (q == 2 || q == 4) ? 1 : 0; }
-template <int RH, int R0, int RT, int CT>  // row tiles R0 .. R0 + RH - 1 of acc
-__device__ __forceinline__ void mfma6_tile(const bf16x8 (&a)[RH][NPL], const bf16x8 (&b)[CT][NPL], f32x4 (&acc)[RT][CT]) {
+template <int RT, int CT>
+__device__ __forceinline__ void mfma6_tile(const bf16x8 (&a)[RT][NPL], const bf16x8 (&b)[CT][NPL], f32x4 (&acc)[RT][CT]) {
 #pragma unroll
     for (int q = 0; q < 6; ++q)
 #pragma unroll
-        for (int rt = 0; rt < RH; ++rt)
+        for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
-                acc[R0 + rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rt][PA(q)], b[ct][PB(q)], acc[R0 + rt][ct], 0, 0, 0);
+                acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rt][PA(q)], b[ct][PB(q)], acc[rt][ct], 0, 0, 0);
 }
 // one accumulator (the heads: a handful of MFMAs per tile)
 __device__ __forceinline__ f32x4 mfma6(const bf16x8 (&a)[NPL], const bf16x8 (&b)[NPL], f32x4 acc) {
@@ -119,14 +119,6 @@ __global__ __launch_bounds__(256) void pack_tiles_f32x_kernel(const float* __res
     }
 }
 
-template <int RT, int CT>
-__device__ __forceinline__ void zero_acc_x(f32x4 (&acc)[RT][CT]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
 // acc = X[0:BM, 0:32*nit] . W^T: weights as three planes of fragment tiles streamed L2 -> registers (ring of PD stages), the A
 // operand from the three slab planes; no barrier inside the loop, one at the end.  Six MFMAs per (row tile, column tile, k-step).
 template <int RT, int NW, int PD>
@@ -153,25 +145,24 @@ struct RowGemmX {
             if (d < nit) gload(d, bq[d]);
         __builtin_amdgcn_sched_barrier(0);
     }
-    template <int R0, int RH>
+    // one k-step: RT x CT independent accumulators, 3 RT A fragments live
     __device__ __forceinline__ void pass(const __bf16* Xb, int it, int r16, int kb, f32x4 (&acc)[RT][CT]) {
-        bf16x8 a[RH][NPL];
+        static_assert(RT <= 2, "a taller tile needs two passes per k-step to keep the A fragments in registers");
+        bf16x8 a[RT][NPL];
 #pragma unroll
         for (int p = 0; p < NPL; ++p)
 #pragma unroll
-            for (int rt = 0; rt < RH; ++rt)
-                a[rt][p] = *reinterpret_cast<const bf16x8*>(Xb + p * G::PLANE + ((R0 + rt) * 16 + r16) * XSB + it * KI + 8 * kb);
-        mfma6_tile<RH, R0, RT, CT>(a, bq[it % PD], acc);
+            for (int rt = 0; rt < RT; ++rt)
+                a[rt][p] = *reinterpret_cast<const bf16x8*>(Xb + p * G::PLANE + (rt * 16 + r16) * XSB + it * KI + 8 * kb);
+        mfma6_tile(a, bq[it % PD], acc);
     }
     __device__ __forceinline__ void run(const __bf16* Xb, f32x4 (&acc)[RT][CT]) {
         const int lane = threadIdx.x & 63, r16 = lane & 15, kb = lane >> 4;
-        zero_acc_x(acc);
+        zero_acc(acc);
 #pragma unroll
         for (int it = 0; it < MAXIT; ++it) {
             if (it >= nit) break;
-            constexpr int RH = RT < 2 ? RT : 2;  // row tiles per pass: 2 x CT independent accumulators, 6 A fragments live
-            pass<0, RH>(Xb, it, r16, kb, acc);
-            if constexpr (RT > 2) pass<2, RH>(Xb, it, r16, kb, acc);
+            pass(Xb, it, r16, kb, acc);
             if (it + PD < nit) {
                 gload(it + PD, bq[it % PD]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -340,9 +331,8 @@ __device__ __forceinline__ void head_forward_mfma_x(const __bf16* Xb, const floa
 // ---------------------------------------------------------------------------------------------------------------
 // rollout step (RT = 1, NW = 8): the launch of rollout_step_bf16_kernel with three-plane operands
 // ---------------------------------------------------------------------------------------------------------------
-template <int PD>  // weight-ring depth
 __global__ __launch_bounds__(512) void rollout_step_f32x_kernel(RolloutArgs a) {
-    constexpr int RT = 1, NW = 8;
+    constexpr int RT = 1, NW = 8, PD = 2;  // PD: weight-ring depth (2 / 4 / 8 measured within 1 us: profiles/r05_f32x_kernel_history.txt)
     touch_kernargs<(int)sizeof(RolloutArgs)>();
     typedef GeoX<RT, NW> G;
     extern __shared__ __align__(16) float smem[];
@@ -428,8 +418,13 @@ __global__ __launch_bounds__(512) void rollout_step_f32x_kernel(RolloutArgs a) {
 // fused optimizer-step kernel (1), f32 through bf16 planes.  Images (plane-major inside every matrix, nrb = ceil(M / 32)):
 //   h  : [2 nets][2][3 planes][16 cb][nrb] tiles    dz : [2 nets][3][3 planes][16 cb][nrb] tiles    st : [3 planes][4 cb][nrb] tiles
 // ---------------------------------------------------------------------------------------------------------------
-template <int RT, int NW, int PD, bool DEC, bool STAMPS = false>  // STAMPS: phase stamps (tools/phase_times.py); the launch instantiates false
-__global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArgs a, __bf16* st_tiles) {
+// 32 rows per workgroup, weight ring of 2 stages.  Measured on one box (profiles/r05_f32x_*): 64-row tiles (half the weight bytes
+// per row, one round of workgroups) 82.2 us against 82.7 us for 32-row tiles; weight-ring depth 1 / 2 / 3: 79.7 / 79.9 / 81.2 us --
+// the launch is bound by neither; the other forms were removed.
+constexpr int FUSED_X_RT = 2, FUSED_X_PD = 2;
+template <bool DEC>  // DEC: the decoupled actor loss (StepArgs.dec)
+__global__ __launch_bounds__(512, 2) void ppo_step_fused_f32x_kernel(StepArgs a, __bf16* st_tiles) {
+    constexpr int RT = FUSED_X_RT, NW = 8, PD = FUSED_X_PD;
     typedef GeoX<RT, NW> G;
     constexpr int BM = G::BM, CT = G::CT;
     extern __shared__ __align__(16) float smem[];
@@ -470,8 +465,6 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
     }
 
     // ---- forward -----------------------------------------------------------------------------------------------------
-    StampsT<STAMPS> ts{a.stamps, 0};
-    ts.mark();
     float* sBias = smem + G::SLAB_FLOATS + G::BIAS_OFF;
     float* sStd = sBias + 3 * HID;
     StatesX<RT, NW> st;
@@ -516,29 +509,21 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
     for (int i = n_out * W4S + tid; i < MAX_OUT * W4S; i += G::NT) W4s[i] = 0.f;
     lds_barrier();
     if (y == 1) StatesX<RT, NW>::tiles(st_tiles, tg.nrb, D, m0, Xb);
-    ts.mark();
     f32x4 acc[RT][CT];
     bf16x4 h3p[NPL][RT][CT];   // h3's planes in the accumulator layout: B operand of the head parameter gradients, and 1 - h3^2
     gemm.run(Xb, acc);
     gemm.prefetch(tiles + Tiles::mat(y, 1), HID / 32);
-    ts.mark();
     epilogue_tanh_x<RT, NW>(acc, sBias, Xb, nullptr, hy, img, tg.nrb, m0);
-    ts.mark();
     gemm.run(Xb, acc);
     gemm.prefetch(tiles + Tiles::mat(y, 2), HID / 32);
-    ts.mark();
     epilogue_tanh_x<RT, NW>(acc, sBias + HID, Xb, nullptr, hy + NPL * img, img, tg.nrb, m0);
-    ts.mark();
     gemm.run(Xb, acc);
-    ts.mark();
     epilogue_tanh_x<RT, NW>(acc, sBias + 2 * HID, Xb, h3p, nullptr, 0, tg.nrb, m0);
-    ts.mark();
 
     // ---- head + loss element math (fused_loss_pass, ppo_step_bf16_parts.h: the bf16 launch's, f32 throughout) --------------------
     head_forward_mfma_x<RT, G::PLANE>(Xb, W4s, sG, sLp);
     lds_barrier();
-    ts.mark();
-    fused_loss_pass<BM, NW, DEC>(a, y, tile, m0, LossLds{b4s, sHead, sLp, sG, sD, sOld, sAct, sAdv, sRet, sStd, reinterpret_cast<double*>(Xb), sNm}, ts);
+    fused_loss_pass<BM, NW, DEC>(a, y, tile, m0, LossLds{b4s, sHead, sLp, sG, sD, sOld, sAct, sAdv, sRet, sStd, reinterpret_cast<double*>(Xb), sNm});
 
     // ---- head parameter gradients per 32-row half tile: dW4[o][j] = sum_rows dOut[row][o] h3[row][j] (see the bf16 kernel) -------
     {
@@ -586,10 +571,9 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
         }
     }
 
-    ts.mark();
     // ---- dZ3 = (dOut . W4) * (1 - h3^2): K = n_out is tiny, f32 operands -> v_mfma_f32_16x16x4_f32 -----------------------------
     gemm.prefetch(tiles + Tiles::mat(y, 4), HID / 32);  // W3^T
-    zero_acc_x(acc);
+    zero_acc(acc);
     for (int ks = 0; ks < (n_out + 3) / 4; ++ks) {
         float av[RT], bv[CT];
 #pragma unroll
@@ -635,7 +619,6 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
     };
     emit(2, h3p, true);
     lds_barrier();
-    ts.mark();
 
     // ---- backward-data chain ---------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -646,16 +629,8 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
         for (int pl = 0; pl < NPL; ++pl) load_tiles_x<RT, CT>(hl[pl], hy + (size_t)((l - 1) * NPL + pl) * img, tg.nrb, m0);
         gemm.run(Xb, acc);
         if (l == 2) gemm.prefetch(tiles + Tiles::mat(y, 3), HID / 32);  // W2^T
-        ts.mark();
         emit(l - 1, hl, l == 2);
         if (l == 2) lds_barrier();
-        ts.mark();
-    }
-    if constexpr (STAMPS) {
-        if (a.stamps != nullptr && blockIdx.x == 0 && blockIdx.y == 1 && threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            a.stamps[ts.n] = (long long)clock64();  // ... and the stores have drained
-        }
     }
 }
 
@@ -666,41 +641,22 @@ __global__ __launch_bounds__(64 * NW, 2) void ppo_step_fused_f32x_kernel(StepArg
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int DWX_THREADS = 384, DWX_NBUF = 3, DWX_BUF_BYTES = NPL * 16 * 1024;
 
-__device__ __forceinline__ void dwx_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a, const __bf16* __restrict__ st_tiles) {
     extern __shared__ __align__(16) char dsm[];
     const rlx_mlp_layout& lay = a.lay;
     const long long M = a.M;
     const int tid = threadIdx.x;
     const int gemm_blocks = round_up(a.gemm_items, 8);
-    int b = blockIdx.x;
+    const int b = blockIdx.x;
 
     if (b >= gemm_blocks) {
-        b -= gemm_blocks;
-        if (b < a.slabs * 2) {
-            if (tid < 256) head_reduce_block(a, b >> 1, b & 1, tid);
-        } else {
-            double* s_red = reinterpret_cast<double*>(dsm);
-            metric_block(a, s_red, tid, DWX_THREADS);
-        }
+        dw_tail_block<DWX_THREADS>(a, b - gemm_blocks, dsm, tid);
         return;
     }
     const int item = (b & 7) * (gemm_blocks >> 3) + (b >> 3);
     if (item >= a.gemm_items) return;
-    const int s = item / 20, w = item % 20;
-    int y, l, i0, j0;
-    if (w < 16) {
-        const int mat = w >> 2, tile = w & 3;
-        y = mat >> 1; l = 1 + (mat & 1); i0 = (tile >> 1) * 128; j0 = (tile & 1) * 128;
-    } else {
-        y = (w - 16) >> 1; l = 0; i0 = ((w - 16) & 1) * 128; j0 = 0;
-    }
+    const DwItem it = dw_item(item);
+    const int s = it.s, y = it.y, l = it.l, i0 = it.i0, j0 = it.j0;
     const int nrb = (int)((M + 31) / 32);
     const size_t img = (size_t)16 * nrb * 512;
     const int Kin = l == 0 ? lay.obs_dim : HID;
@@ -756,7 +712,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
         for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum[4] = {0.f, 0.f, 0.f, 0.f};
     for (int kb = 0; kb < nkb; ++kb) {
-        dwx_barrier();  // hand-off kb
+        dwr_barrier();  // hand-off kb
         const char* buf = dsm + (kb % DWX_NBUF) * DWX_BUF_BYTES + lane * 16;
         bf16x8 fb[4][NPL];
 #pragma unroll
@@ -781,7 +737,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
             }
         }
     }
-    dwx_barrier();  // every compute wave has read its last fragments (the loaders are gone): the ring becomes the store staging area
+    dwr_barrier();  // every compute wave has read its last fragments (the loaders are gone): the ring becomes the store staging area
     float* slab = a.grads + (size_t)s * lay.n_params;
     float* dW = slab + lay.off_w[y][l];
     const bool vec_ok = (lay.n_params & 3) == 0 && (reinterpret_cast<uintptr_t>(a.grads) & 15) == 0;
@@ -852,26 +808,22 @@ int pack_tiles_f32x(const float* params, const rlx_mlp_layout& lay, void* tiles,
 
 int launch_rollout_f32x(const RolloutArgs& a, int blocks, hipStream_t st) {
     const size_t lds = GeoX<1, 8>::LDS_BYTES;
-    if (int rc = set_lds(rollout_step_f32x_kernel<2>, lds)) return rc;
-    hipLaunchKernelGGL(rollout_step_f32x_kernel<2>, dim3(blocks), dim3(512), lds, st, a);
+    if (int rc = set_lds(rollout_step_f32x_kernel, lds)) return rc;
+    hipLaunchKernelGGL(rollout_step_f32x_kernel, dim3(blocks), dim3(512), lds, st, a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
 
 int launch_step_f32x(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st) {
     __bf16* stt = static_cast<__bf16*>(st_tiles);
-#define RLX_F32X_LAUNCH(RTV, PDV, DECV, STV)                                                                                       \
-    {                                                                                                                              \
-        const size_t lds = GeoX<RTV, 8>::LDS_BYTES;                                                                                \
-        if (int rc = set_lds(ppo_step_fused_f32x_kernel<RTV, 8, PDV, DECV, STV>, lds)) return rc;                                \
-        hipLaunchKernelGGL((ppo_step_fused_f32x_kernel<RTV, 8, PDV, DECV, STV>), dim3(tiles, 2), dim3(512), lds, st, a, stt);     \
+    const size_t lds = GeoX<FUSED_X_RT, 8>::LDS_BYTES;  // `tiles` counts 32-row tiles (plan_step)
+    if (a.dec.on) {
+        if (int rc = set_lds(ppo_step_fused_f32x_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(ppo_step_fused_f32x_kernel<true>, dim3(tiles, 2), dim3(512), lds, st, a, stt);
+    } else {
+        if (int rc = set_lds(ppo_step_fused_f32x_kernel<false>, lds)) return rc;
+        hipLaunchKernelGGL(ppo_step_fused_f32x_kernel<false>, dim3(tiles, 2), dim3(512), lds, st, a, stt);
     }
-    // `tiles` counts 32-row tiles (plan_step).  Measured on one box (profiles/r05_f32x_*): 64-row tiles (half the weight bytes
-    // per row, one round of workgroups) 82.2 us against 82.7 us for 32-row tiles; weight-ring depth 1 / 2 / 3: 79.7 / 79.9 / 81.2 us
-    // -- the launch is bound by neither.  32 rows, depth 2 it is; the other forms were removed.
-    if (a.dec.on) RLX_F32X_LAUNCH(2, 2, true, false)
-    else RLX_F32X_LAUNCH(2, 2, false, false)
-#undef RLX_F32X_LAUNCH
     RLX_LAUNCH_CHECK();
     const size_t rlds = (size_t)DWX_NBUF * DWX_BUF_BYTES;
     if (int rc = set_lds(ppo_step_dw_f32x_kernel, rlds)) return rc;
