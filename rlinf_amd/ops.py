@@ -357,28 +357,54 @@ def raw_adv(scores: torch.Tensor, loss_mask: torch.Tensor, normalize: bool = Fal
 _LEVELS = ("action_level", "token_level", "chunk_level")
 
 
+def _adv_geometry(logprob_type: str, action_dim: int, chunks: int, reward_type: Optional[str] = None):
+    """(raw_per_adv, sub_per_adv, metric_unbroadcast): raw log-probs and ratios under one advantage element
+    (algorithms/utils.py:325-356).  With reward_type='chunk_level' the advantage / mask / value tensors are per env-step ([bsz],
+    utils.py:296-308) while token-level log-probs keep one loss element per action dimension of every chunk."""
+    if reward_type == "chunk_level" and logprob_type == "token_level":  # one advantage per env step, a ratio per raw log-prob
+        return action_dim * chunks, action_dim * chunks, 0
+    if reward_type == "chunk_level" and logprob_type == "action_level" and chunks > 1:
+        # ratio [bsz, C] against [bsz, 1] advantages / mask: one advantage element per env step, C ratios under it, each the
+        # sum of action_dim raw log-probs; the ratio metrics keep the un-broadcast mask count (PpoLossParams.metric_unbroadcast)
+        return action_dim * chunks, chunks, 1
+    if logprob_type == "action_level":
+        return action_dim, 1, 0
+    if logprob_type == "token_level":
+        return action_dim, action_dim, 0
+    if logprob_type == "chunk_level":
+        return action_dim * chunks, 1, 0
+    raise RlxError(f"logprob_type must be one of {_LEVELS}")
+
+
 def _loss_geometry(logprobs: torch.Tensor, logprob_type: str, action_dim: int, reward_type: Optional[str] = None):
-    """(n_adv, raw_per_adv, sub_per_adv) for a [bsz, C*A] log-prob tensor (algorithms/utils.py:325-356).  With
-    reward_type='chunk_level' the advantage / mask / value tensors are per env-step ([bsz], utils.py:296-308) while
-    token-level log-probs keep one loss element per action dimension of every chunk: bsz x (C*A) x (C*A)."""
-    bsz = logprobs.shape[0]
-    per_row = logprobs.numel() // max(bsz, 1)
+    """(n_adv, chunks) for a [bsz, C*A] log-prob tensor: the advantage elements it spans and its action chunks per row."""
+    per_row = logprobs.numel() // max(logprobs.shape[0], 1)
     if logprob_type not in _LEVELS:
         raise RlxError(f"logprob_type must be one of {_LEVELS}, got {logprob_type!r}")
     if per_row % action_dim != 0:
         raise RlxError(f"logprobs row of {per_row} elements is not a multiple of action_dim={action_dim}")
     chunks = per_row // action_dim
-    if reward_type == "chunk_level" and logprob_type == "token_level":
-        return bsz, per_row, per_row
-    if reward_type == "chunk_level" and logprob_type == "action_level" and chunks > 1:
-        # ratio [bsz, C] against [bsz, 1] advantages / mask: one advantage element per env step, C ratios under it, each the
-        # sum of action_dim raw log-probs; the ratio metrics keep the un-broadcast mask count (PpoLossParams.metric_unbroadcast)
-        return bsz, per_row, chunks
-    if logprob_type == "action_level":
-        return bsz * chunks, action_dim, 1
-    if logprob_type == "token_level":
-        return bsz * chunks, action_dim, action_dim
-    return bsz, per_row, 1
+    return logprobs.shape[0] * per_row // _adv_geometry(logprob_type, action_dim, chunks, reward_type)[0], chunks
+
+
+def _loss_forward(ctx, logprobs, values, params: PpoLossParams, n_adv: int, workspace_bytes, launch):
+    """The forward both loss nodes share: per-element gradient factors, the metric row and the workspace are allocated here,
+    ``launch(lp, g_lp, g_v, out, ws, ws_bytes)`` issues the node's own forward, ``ctx`` keeps what rlx_ppo_loss_bwd needs."""
+    dev = logprobs.device
+    g_lp = torch.empty((n_adv * params.sub_per_adv,), dtype=torch.float32, device=dev)
+    g_v = torch.empty((n_adv,), dtype=torch.float32, device=dev) if params.has_critic else None
+    out = torch.empty((_lib.PPO_OUT_FLOATS,), dtype=torch.float32, device=dev)
+    ws_bytes = workspace_bytes(n_adv)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        launch(logprobs.contiguous(), g_lp, g_v, out, ws, ws_bytes)
+    ctx.save_for_backward(g_lp, g_v if g_v is not None else out, out)
+    ctx.has_critic = bool(params.has_critic)
+    ctx.geom = (n_adv, params.raw_per_adv, params.sub_per_adv)
+    ctx.lp_shape = logprobs.shape
+    ctx.v_shape = None if values is None else values.shape
+    ctx.mark_non_differentiable(out)
+    return out[0].clone(), out
 
 
 class _PpoLossFn(torch.autograd.Function):
@@ -386,25 +412,14 @@ class _PpoLossFn(torch.autograd.Function):
     def forward(ctx, logprobs, values, old_logprobs, advantages, prev_values, returns, loss_mask, loss_mask_sum,
                 params: PpoLossParams, n_adv: int):
         lib = _lib.load()
-        dev = logprobs.device
-        lp = logprobs.contiguous()
-        g_lp = torch.empty((n_adv * params.sub_per_adv,), dtype=torch.float32, device=dev)
-        g_v = torch.empty((n_adv,), dtype=torch.float32, device=dev) if params.has_critic else None
-        out = torch.empty((_lib.PPO_OUT_FLOATS,), dtype=torch.float32, device=dev)
-        ws_bytes = lib.rlx_ppo_loss_workspace_bytes(n_adv)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+
+        def launch(lp, g_lp, g_v, out, ws, ws_bytes):
             _lib.check(lib.rlx_ppo_loss_fwd(lp.data_ptr(), old_logprobs.data_ptr(), advantages.data_ptr(), _ptr(values),
                                             _ptr(prev_values), _ptr(returns), _ptr(loss_mask), _ptr(loss_mask_sum), n_adv,
                                             byref(params), g_lp.data_ptr(), _ptr(g_v), out.data_ptr(), ws.data_ptr(),
-                                            ws_bytes, _stream_ptr(dev)), "rlx_ppo_loss_fwd")
-        ctx.save_for_backward(g_lp, g_v if g_v is not None else out, out)
-        ctx.has_critic = bool(params.has_critic)
-        ctx.geom = (n_adv, params.raw_per_adv, params.sub_per_adv)
-        ctx.lp_shape = logprobs.shape
-        ctx.v_shape = None if values is None else values.shape
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+                                            ws_bytes, _stream_ptr(lp.device)), "rlx_ppo_loss_fwd")
+
+        return _loss_forward(ctx, logprobs, values, params, n_adv, lib.rlx_ppo_loss_workspace_bytes, launch)
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_out):
@@ -439,8 +454,7 @@ def ppo_loss(logprobs: torch.Tensor, old_logprobs: torch.Tensor, advantages: tor
     for name, t in (("logprobs", logprobs), ("old_logprobs", old_logprobs), ("advantages", advantages)):
         if t.dtype != torch.float32:
             raise RlxError(f"{name} must be float32 to keep numerical stability")
-    n_adv, raw, sub = _loss_geometry(logprobs, logprob_type, action_dim, reward_type)
-    unbroadcast = reward_type == "chunk_level" and logprob_type == "action_level" and sub > 1
+    n_adv, chunks = _loss_geometry(logprobs, logprob_type, action_dim, reward_type)
     if old_logprobs.numel() != logprobs.numel():
         raise RlxError("old_logprobs must have the shape of logprobs")
     if advantages.numel() != n_adv:
@@ -467,20 +481,11 @@ def ppo_loss(logprobs: torch.Tensor, old_logprobs: torch.Tensor, advantages: tor
             raise RlxError(f"loss_mask_sum has {msum.numel()} elements, expected {n_adv}")
     if clip_ratio_c is not None and not clip_ratio_c > 1.0:
         raise AssertionError("clip_ratio_c must be greater than 1.0")
-    p = PpoLossParams()
-    p.ratio_lo, p.ratio_hi = float(1.0 - clip_ratio_low), float(1.0 + clip_ratio_high)
-    p.clip_ratio_c = float(clip_ratio_c) if clip_ratio_c is not None else 0.0
-    p.use_dual_clip = int(clip_ratio_c is not None)
-    p.clip_log_ratio_min = float(clip_log_ratio_min) if clip_log_ratio_min is not None else 0.0
-    p.clip_log_ratio_max = float(clip_log_ratio_max) if clip_log_ratio_max is not None else 0.0
-    p.use_clip_log_ratio_min = int(clip_log_ratio_min is not None)
-    p.use_clip_log_ratio_max = int(clip_log_ratio_max is not None)
-    p.value_clip = float(value_clip) if has_critic else 0.0
-    p.huber_delta = float(huber_delta) if has_critic else 0.0
-    p.has_critic = int(has_critic)
-    p.critic_warmup = int(bool(critic_warmup))
-    p.max_episode_steps = int(max_episode_steps) if max_episode_steps else 0
-    p.raw_per_adv, p.sub_per_adv, p.metric_unbroadcast = raw, sub, int(unbroadcast)
+    p = make_ppo_params(logprob_type=logprob_type, action_dim=action_dim, chunks=chunks, clip_ratio_low=clip_ratio_low,
+                        clip_ratio_high=clip_ratio_high, value_clip=value_clip, huber_delta=huber_delta,
+                        max_episode_steps=max_episode_steps, clip_ratio_c=clip_ratio_c, clip_log_ratio_min=clip_log_ratio_min,
+                        clip_log_ratio_max=clip_log_ratio_max, critic_warmup=critic_warmup, has_critic=has_critic,
+                        reward_type=reward_type)
     v = values.contiguous() if has_critic else None
     if decoupled is not None:
         dp, prox, versions = _decoupled_params(p, logprobs, **decoupled)
@@ -523,27 +528,15 @@ class _DecoupledLossFn(torch.autograd.Function):
     def forward(ctx, logprobs, values, old_logprobs, advantages, prev_values, returns, loss_mask, loss_mask_sum,
                 proximal_logprobs, versions, dp, n_adv: int):
         lib = _lib.load()
-        dev = logprobs.device
-        params = dp.ppo
-        lp = logprobs.contiguous()
-        g_lp = torch.empty((n_adv * params.sub_per_adv,), dtype=torch.float32, device=dev)
-        g_v = torch.empty((n_adv,), dtype=torch.float32, device=dev) if params.has_critic else None
-        out = torch.empty((_lib.PPO_OUT_FLOATS,), dtype=torch.float32, device=dev)
-        ws_bytes = lib.rlx_decoupled_loss_workspace_bytes(n_adv)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+
+        def launch(lp, g_lp, g_v, out, ws, ws_bytes):
             _lib.check(lib.rlx_decoupled_loss_fwd(
                 lp.data_ptr(), old_logprobs.data_ptr(), _ptr(proximal_logprobs), _ptr(versions), advantages.data_ptr(),
                 _ptr(values), _ptr(prev_values), _ptr(returns), _ptr(loss_mask), _ptr(loss_mask_sum), n_adv, byref(dp),
-                g_lp.data_ptr(), _ptr(g_v), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(dev)),
+                g_lp.data_ptr(), _ptr(g_v), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(lp.device)),
                 "rlx_decoupled_loss_fwd")
-        ctx.save_for_backward(g_lp, g_v if g_v is not None else out, out)
-        ctx.has_critic = bool(params.has_critic)
-        ctx.geom = (n_adv, params.raw_per_adv, params.sub_per_adv)
-        ctx.lp_shape = logprobs.shape
-        ctx.v_shape = None if values is None else values.shape
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+
+        return _loss_forward(ctx, logprobs, values, dp.ppo, n_adv, lib.rlx_decoupled_loss_workspace_bytes, launch)
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_out):
@@ -566,18 +559,7 @@ def make_ppo_params(*, logprob_type="action_level", action_dim=8, chunks=1, clip
     p.huber_delta = float(huber_delta) if has_critic else 0.0
     p.has_critic, p.critic_warmup = int(has_critic), int(bool(critic_warmup))
     p.max_episode_steps = int(max_episode_steps) if max_episode_steps else 0
-    if reward_type == "chunk_level" and logprob_type == "token_level":  # one advantage per env step, a ratio per raw log-prob
-        p.raw_per_adv, p.sub_per_adv = action_dim * chunks, action_dim * chunks
-    elif reward_type == "chunk_level" and logprob_type == "action_level" and chunks > 1:  # ... a ratio per action chunk
-        p.raw_per_adv, p.sub_per_adv, p.metric_unbroadcast = action_dim * chunks, chunks, 1
-    elif logprob_type == "action_level":
-        p.raw_per_adv, p.sub_per_adv = action_dim, 1
-    elif logprob_type == "token_level":
-        p.raw_per_adv, p.sub_per_adv = action_dim, action_dim
-    elif logprob_type == "chunk_level":
-        p.raw_per_adv, p.sub_per_adv = action_dim * chunks, 1
-    else:
-        raise RlxError(f"logprob_type must be one of {_LEVELS}")
+    p.raw_per_adv, p.sub_per_adv, p.metric_unbroadcast = _adv_geometry(logprob_type, action_dim, chunks, reward_type)
     return p
 
 
@@ -891,6 +873,26 @@ def _set_deferred(p: AdamwParams, deferred: Optional[dict]):
         p.deferred_range[k][0], p.deferred_range[k][1] = int(b), int(e)
 
 
+def _adamw_params(groups: list, slabs: int, step: int, *, betas, eps, weight_decay, max_grad_norm, grad_scale, tile_layout, tiles,
+                  deferred, sync) -> AdamwParams:
+    """rlx_adamw_params for ``groups`` = [(begin, end, lr), ...] over ``slabs`` gradient slabs."""
+    if len(groups) > _lib.ADAMW_MAX_GROUPS:
+        raise RlxError("too many parameter groups")
+    p = AdamwParams()
+    p.beta1, p.beta2, p.eps, p.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    p.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
+    p.step, p.n_groups, p.grad_partials, p.grad_scale = int(step), len(groups), int(slabs), float(grad_scale)
+    for k, (b, e, lr) in enumerate(groups):
+        p.groups[k] = AdamwGroup(int(b), int(e), float(lr))
+    if tile_layout is not None and tiles is not None:  # keep the fragment-tile weight image in step with the parameters
+        p.tile_layout, p.tiles = ctypes.pointer(tile_layout), tiles.data_ptr()
+        p.tiles_bf16 = int(tiles.dtype == torch.bfloat16)
+    _set_deferred(p, deferred)
+    if sync is not None:
+        p.sync_words = sync.data_ptr()
+    return p
+
+
 def clip_adamw_step_(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
                      groups: list, step: int, *, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
                      max_grad_norm: float = 0.5, grad_scale: float = 1.0, stats: Optional[torch.Tensor] = None,
@@ -910,21 +912,9 @@ def clip_adamw_step_(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.T
             raise RlxError("clip_adamw_step_ needs contiguous float32 buffers")
     if grads.numel() % max(n, 1) != 0 or exp_avg.numel() != n or exp_avg_sq.numel() != n:
         raise RlxError("buffer sizes do not match")
-    slabs = grads.numel() // max(n, 1)
-    if len(groups) > _lib.ADAMW_MAX_GROUPS:
-        raise RlxError("too many parameter groups")
-    p = AdamwParams()
-    p.beta1, p.beta2, p.eps, p.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
-    p.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
-    p.step, p.n_groups, p.grad_partials, p.grad_scale = int(step), len(groups), int(slabs), float(grad_scale)
-    for k, (b, e, lr) in enumerate(groups):
-        p.groups[k] = AdamwGroup(int(b), int(e), float(lr))
-    if tile_layout is not None and tiles is not None:  # keep the fragment-tile weight image in step with the parameters
-        p.tile_layout, p.tiles = ctypes_pointer(tile_layout), tiles.data_ptr()
-        p.tiles_bf16 = int(tiles.dtype == torch.bfloat16)
-    _set_deferred(p, deferred)
-    if sync is not None:
-        p.sync_words = sync.data_ptr()
+    p = _adamw_params(groups, grads.numel() // max(n, 1), step, betas=betas, eps=eps, weight_decay=weight_decay,
+                      max_grad_norm=max_grad_norm, grad_scale=grad_scale, tile_layout=tile_layout, tiles=tiles, deferred=deferred,
+                      sync=sync)
     if stats is None:
         stats = torch.empty((2,), dtype=torch.float32, device=dev)
     ws_bytes = lib.rlx_adamw_workspace_bytes(n)
@@ -985,6 +975,17 @@ def mlp_pack(params: torch.Tensor, layout: MlpLayout, packed: Optional[torch.Ten
     return packed
 
 
+def _rollout_outputs(out: Optional[tuple], M: int, layout: MlpLayout, dev, who: str) -> tuple:
+    """(action [M,act], logprob [M,act], value [M,val]): the caller's rows checked (e.g. the trajectory buffer's), or new ones."""
+    if out is None:
+        action = torch.empty((M, layout.act_dim), dtype=torch.float32, device=dev)
+        return action, torch.empty_like(action), torch.empty((M, layout.val_dim), dtype=torch.float32, device=dev)
+    for t, w in zip(out, (layout.act_dim, layout.act_dim, layout.val_dim)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * w:
+            raise RlxError(f"{who}: out tensors must be contiguous float32 of the right size")
+    return tuple(out)
+
+
 def mlp_rollout(params: torch.Tensor, packed: torch.Tensor, layout: MlpLayout, states: torch.Tensor,
                 eps: Optional[torch.Tensor], out: Optional[tuple] = None):
     """states [M,D], eps [M,act]|None -> (action [M,act], logprob [M,act], value [M,val])."""
@@ -997,15 +998,7 @@ def mlp_rollout(params: torch.Tensor, packed: torch.Tensor, layout: MlpLayout, s
     e = _as_f32(eps, "eps")
     if e is not None and tuple(e.shape) != (M, layout.act_dim):
         raise RlxError(f"eps must be [{M}, {layout.act_dim}]")
-    if out is not None:  # write straight into caller-owned rows (e.g. the trajectory buffer)
-        action, logprob, value = out
-        for t, w in ((action, layout.act_dim), (logprob, layout.act_dim), (value, layout.val_dim)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * w:
-                raise RlxError("mlp_rollout: out tensors must be contiguous float32 of the right size")
-    else:
-        action = torch.empty((M, layout.act_dim), dtype=torch.float32, device=dev)
-        logprob = torch.empty_like(action)
-        value = torch.empty((M, layout.val_dim), dtype=torch.float32, device=dev)
+    action, logprob, value = _rollout_outputs(out, M, layout, dev, "mlp_rollout")
     with torch.cuda.device(dev):
         _lib.check(lib.rlx_mlp_rollout(params.data_ptr(), packed.data_ptr(), byref(layout), st.data_ptr(), _ptr(e), M,
                                        action.data_ptr(), logprob.data_ptr(), value.data_ptr(), _stream_ptr(dev)),
@@ -1134,15 +1127,7 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
         e = _as_f32(eps, "eps")
         if e is not None and tuple(e.shape) != (M, layout.act_dim):
             raise RlxError(f"eps must be [{M}, {layout.act_dim}]")
-        if out is not None:
-            action, logprob, value = out
-            for t, w in ((action, layout.act_dim), (logprob, layout.act_dim), (value, layout.val_dim)):
-                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * w:
-                    raise RlxError("mlp_rollout_step: out tensors must be contiguous float32 of the right size")
-        else:
-            action = torch.empty((M, layout.act_dim), dtype=torch.float32, device=dev)
-            logprob = torch.empty_like(action)
-            value = torch.empty((M, layout.val_dim), dtype=torch.float32, device=dev)
+        action, logprob, value = _rollout_outputs(out, M, layout, dev, "mlp_rollout_step")
         if states_copy is not None and (states_copy.dtype != torch.float32 or not states_copy.is_contiguous()
                                         or states_copy.numel() != s_.numel()):
             raise RlxError("mlp_rollout_step: states_copy must be a contiguous float32 tensor shaped like states")
@@ -1190,7 +1175,6 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
 
 
 def ctypes_pointer(layout: MlpLayout):
-    import ctypes
     return ctypes.pointer(layout)
 
 
@@ -1284,22 +1268,14 @@ class PreparedAdamw:
         rank's slabs, the reduced gradient (scaled by grad_scale = 1 / world_size) lands in grad_flat, then clip + AdamW."""
         self._lib = _lib.load()
         n = params.numel()
-        p = AdamwParams()
-        p.beta1, p.beta2, p.eps, p.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
-        p.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
-        p.step, p.n_groups, p.grad_partials, p.grad_scale = 0, len(groups), grads.numel() // n, float(grad_scale)
-        for k, (b, e, lr) in enumerate(groups):
-            p.groups[k] = AdamwGroup(int(b), int(e), float(lr))
-        if tile_layout is not None and tiles is not None:
-            p.tile_layout, p.tiles, p.tiles_bf16 = ctypes_pointer(tile_layout), tiles.data_ptr(), int(tiles.dtype == torch.bfloat16)
-        _set_deferred(p, deferred)
+        # one GPU: slab sum + norm + clip + AdamW as one launch.  Over xGMI: the exchange INSIDE that launch, when the communicator's
+        # start-up validation has passed it (XgmiAllReduce.one_launch); otherwise the exchange's launch chain with its hand-shakes
+        p = _adamw_params(groups, grads.numel() // n, 0, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                          grad_scale=grad_scale, tile_layout=tile_layout, tiles=tiles, deferred=deferred,
+                          sync=sync if (xgmi is None or getattr(xgmi, "one_launch", False)) else None)
         self.deferred = deferred  # (a data-parallel caller that collapses the slabs itself -- RCCL path -- applies it there)
         if deferred is not None and deferred_in_caller:
             p.deferred_scale = None  # the caller sums (and scales: sum_slabs(deferred=...)) the slabs in front of its all-reduce
-        # one GPU: slab sum + norm + clip + AdamW as one launch.  Over xGMI: the exchange INSIDE that launch, when the communicator's
-        # start-up validation has passed it (XgmiAllReduce.one_launch); otherwise the exchange's launch chain with its hand-shakes
-        if sync is not None and (xgmi is None or getattr(xgmi, "one_launch", False)):
-            p.sync_words = sync.data_ptr()
         self._keep = (params, grads, exp_avg, exp_avg_sq, stats, step_state, workspace, tile_layout, tiles, p, xgmi, grad_flat, deferred, sync)
         if xgmi is not None:
             self._fn, self._name = self._lib.rlx_xgmi_clip_adamw_step, "rlx_xgmi_clip_adamw_step"

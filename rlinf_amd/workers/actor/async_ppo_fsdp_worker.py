@@ -26,12 +26,13 @@ from ..._lib import DPPO_OUT_NAMES, PPO_ACTOR_GRAD_SCALE, PPO_OUT_FLOATS
 from ...algorithms.losses import _CRITIC_KEYS, _DECOUPLED_KEYS, _EV_MAP, explained_variance_from_stats
 from ...algorithms.registry import calculate_adv_and_returns
 from ...scheduler import all_reduce_flat_
-from ...utils.pending import PendingMetrics
 from .embodied_fsdp_actor_worker import CRITIC_EXPLAINED_VARIANCE_KEY, EmbodiedFSDPActor
 
 
 class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
     """Embodied learner for async PPO / decoupled actor-critic training."""
+
+    METRIC_ROW_FLOATS = PPO_OUT_FLOATS + 2  # + the entropy bonus's part of the loss, the entropy loss
 
     def __init__(self, cfg, ctx=None):
         super().__init__(cfg, ctx)
@@ -231,105 +232,59 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
         return (self.fused_step and self.critic_warmup_steps == 0
                 and (msum is None or (msum.dtype == torch.int64 and msum.numel() == flat["advantages"].numel())))
 
-    def _decoupled_loss_params(self):
+    def _loss_params(self, critic_warmup: bool):
         alg, m = self.cfg.algorithm, self.cfg.actor.model
         return ops.make_ppo_params(
             logprob_type=alg.logprob_type, action_dim=int(m.get("action_dim", 7)), chunks=int(m.get("num_action_chunks", 1)),
             clip_ratio_low=alg.clip_ratio_low, clip_ratio_high=alg.clip_ratio_high, value_clip=alg.get("value_clip"),
             huber_delta=alg.get("huber_delta"), max_episode_steps=self.cfg.env.train.get("max_episode_steps"),
-            clip_ratio_c=alg.get("clip_ratio_c", 3.0), critic_warmup=False, has_critic=True,
+            clip_ratio_c=alg.get("clip_ratio_c", 3.0), critic_warmup=critic_warmup, has_critic=True,
             reward_type=alg.get("reward_type", "action_level"))
 
-    def _entropy_bonus_deferred(self, mb: dict, g: torch.Tensor, row: torch.Tensor, ent_row: torch.Tensor):
+    def _entropy_bonus_deferred(self, mb: dict, g: torch.Tensor, row: torch.Tensor):
         """:449-462 behind a decoupled fused step: the decoupled row keeps slot 19 for the average version, so the bonus goes
         through a scratch row; the logstd slab is in sum form -> the bonus is pre-divided by the row's actor scale."""
+        ent_row = self._ent_row
         ent_row.zero_()
         ent_row[18] = row[DPPO_OUT_NAMES["mask_count"]]
         self._entropy_bonus(mb, g, ent_row, actor_scale=row[PPO_ACTOR_GRAD_SCALE:PPO_ACTOR_GRAD_SCALE + 1])
         row[PPO_OUT_FLOATS] = ent_row[0]
         row[PPO_OUT_FLOATS + 1] = ent_row[19]
 
-    def _fused_plan(self, flat: dict, N: int, rows: torch.Tensor, norms: torch.Tensor, grads: torch.Tensor, ws: dict, n_global: int,
-                    per_rank: int, accum: int, micro: int) -> list:
-        """Every launch of the update phase marshalled once: [(micro-batch calls, AdamW call)] per optimizer step."""
-        m, o, alg = self.model, self.cfg.actor.optim, self.cfg.algorithm
-        epochs = int(alg.get("update_epoch", 1))
-        pkey = ("aplan", N, micro, accum, epochs, tuple((k, t.data_ptr()) for k, t in flat.items()), rows.data_ptr())
-        if self._ws.get("aplan_key") == pkey:
-            return self._ws["aplan"]
-        bf16 = m.compute_dtype == torch.bfloat16
-        tiles = m.tiles() if self.optimizer_writes_tiles else None
-        lp = self._decoupled_loss_params()
-        bonus = float(alg.get("entropy_bonus", 0) or 0)
-        ent_row = torch.zeros(PPO_OUT_FLOATS, device=self.device)
-        plan, step = [], 0
-        for _ in range(epochs):
-            for i in range(n_global):
-                calls, step_rows = [], rows[step * accum:(step + 1) * accum]
-                for j in range(accum):
-                    lo = i * per_rank + j * micro
-                    mb = {k: v[lo:lo + micro] for k, v in flat.items()}
-                    if mb.get("proximal_values") is not None:  # :419-421
-                        mb["prev_values"] = mb["proximal_values"]
-                    if mb.get("loss_mask") is not None:
-                        mb["loss_mask"] = mb["loss_mask"].view(torch.uint8)
-                    row, g = step_rows[j], grads[j * ws["slabs"]:(j + 1) * ws["slabs"]]
-                    dec = ops.decoupled_step_args(lp, mb, current_version=int(self.version) + 1,
-                                                  behave_weight_threshold=alg.get("behave_weight_threshold"),
-                                                  current_version_dev=self._version_dev)
-                    calls.append(ops.PreparedPpoStep(m.flat.data, m.layout, lp, mb, g, row[:PPO_OUT_FLOATS], ws["step_ws"],
-                                                     grad_out=1.0 / accum, tiles=tiles, bf16=bf16, decoupled=dec))
-                    if bonus > 0:
-                        calls.append(lambda _s, mb=mb, g=g, r=row: self._entropy_bonus_deferred(mb, g, r, ent_row))
-                multi, xg = self._exchange, self._xgmi
-                adam = ops.PreparedAdamw(
-                    m.flat.data, self.grad_flat if (multi and xg is None) else grads, self.exp_avg, self.exp_avg_sq, self.groups,
-                    betas=(o.adam_beta1, o.adam_beta2), eps=o.adam_eps, weight_decay=o.weight_decay, max_grad_norm=o.clip_grad,
-                    grad_scale=1.0 / self._world_size if multi else 1.0, stats=norms[step], step_state=self.step_state,
-                    workspace=self.adamw_ws, tile_layout=m.layout if tiles is not None else None, tiles=tiles, xgmi=xg,
-                    grad_flat=self.grad_flat if xg is not None else None,
-                    deferred=ops.deferred_actor_scale(m.layout, step_rows[:, :PPO_OUT_FLOATS], accum),
-                    deferred_in_caller=multi and xg is None, sync=self.adamw_sync)
-                plan.append((calls, adam))
-                step += 1
-        self._ws["aplan_key"], self._ws["aplan"] = pkey, plan
-        return plan
+    def _micro_batch_calls(self, lp, mb: dict, g: torch.Tensor, row: torch.Tensor, step_ws: torch.Tensor) -> list:
+        """The decoupled loss inside rlx_ppo_step; the actor network's gradients leave it in sum form (_step_deferred)."""
+        m, alg = self.model, self.cfg.algorithm
+        if mb.get("proximal_values") is not None:  # :419-421
+            mb["prev_values"] = mb["proximal_values"]
+        if mb.get("loss_mask") is not None:
+            mb["loss_mask"] = mb["loss_mask"].view(torch.uint8)
+        dec = ops.decoupled_step_args(lp, mb, current_version=int(self.version) + 1,
+                                      behave_weight_threshold=alg.get("behave_weight_threshold"),
+                                      current_version_dev=self._version_dev)
+        calls = [ops.PreparedPpoStep(m.flat.data, m.layout, lp, mb, g, row[:PPO_OUT_FLOATS], step_ws, grad_out=self._grad_out_host,
+                                     tiles=m.tiles() if self.optimizer_writes_tiles else None,
+                                     bf16=m.compute_dtype == torch.bfloat16, decoupled=dec)]
+        if float(alg.get("entropy_bonus", 0) or 0) > 0:
+            calls.append(lambda _stream: self._entropy_bonus_deferred(mb, g, row))
+        return calls
+
+    def _step_deferred(self, step_rows: torch.Tensor, accum: int) -> dict:
+        return ops.deferred_actor_scale(self.model.layout, step_rows[:, :PPO_OUT_FLOATS], accum)
+
+    def _capturable(self) -> bool:
+        """At world_size > 1 only over the xGMI exchange (pure kernels): this learner does not capture RCCL."""
+        return not self._exchange or self._xgmi is not None
 
     def _run_training_fused(self, flat: dict, N: int, n_global: int, per_rank: int, accum: int, micro: int) -> dict:
-        alg, m = self.cfg.algorithm, self.model
-        n_steps = n_global * int(alg.get("update_epoch", 1))
-        ws = self._minibatch_workspace(micro)
-        gkey = ("grads", micro, accum)
-        if gkey not in self._ws:
-            self._ws[gkey] = torch.zeros((ws["slabs"] * accum, m.n_params), dtype=torch.float32, device=self.device)
-        grads = self._ws[gkey]
-        mkey = ("arows", n_steps, accum)
-        if mkey not in self._ws:
-            self._ws[mkey] = (torch.zeros(n_steps * accum, PPO_OUT_FLOATS + 2, device=self.device),
-                              torch.zeros(n_steps, 2, device=self.device))
-        rows, norms = self._ws[mkey]
+        n_steps = n_global * int(self.cfg.algorithm.get("update_epoch", 1))
+        _, grads, rows, norms = self._update_buffers(micro, accum, n_steps)
         if getattr(self, "_version_dev", None) is None:
             self._version_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self._ent_row = torch.zeros(PPO_OUT_FLOATS, device=self.device)  # _entropy_bonus_deferred's scratch row
         self._version_dev.fill_(float(int(self.version) + 1))  # read by the launches when they EXECUTE: a replayed graph sees it
-        self._grad_out_host = 1.0 / accum
-        plan = self._fused_plan(flat, N, rows, norms, grads, ws, n_global, per_rank, accum, micro)
-        gkey2 = ("agraph", self._ws["aplan_key"])
-        # (at world_size > 1 only over the xGMI exchange -- pure kernels; RCCL capture needs the all-rank agreement of the base class)
-        use_graph = self.enable_hip_graph and self.lr_scheduler.is_static and (not self._exchange or self._xgmi is not None)
+        plan = self._update_plan(flat, N, n_global, per_rank, accum)
         self._lr_log = []
-        if use_graph and self._ws.get("agraph_key") == gkey2:
-            self._ws["agraph"].replay()
-            m.mark_updated(tiles_fresh=self.optimizer_writes_tiles)
-            self.optimizer_steps += n_steps
-        else:
-            self._exec_plan(plan, grads)  # real run (also the warm-up before a capture)
-            if use_graph:
-                torch.cuda.synchronize(self.device)
-                before, g = self.optimizer_steps, torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._exec_plan(plan, grads)
-                self.optimizer_steps = before  # capture records, it does not execute
-                self._ws["agraph_key"], self._ws["agraph"] = gkey2, g
+        self._run_or_replay(self._plan_key, lambda: self._exec_plan(plan, grads), n_steps)
         out = self._collect_decoupled_metrics(rows, norms, accum, flat.get("versions") is not None)
         if self._xgmi is not None and not self.defer_host_reads:
             self._xgmi.check_status()  # a peer that never published its gradient: raise instead of training on garbage
@@ -415,16 +370,8 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
             all_reduce_flat_(ev, self.ctx)
         vec = torch.cat([avg, ev, counted.sum().view(1)])
         current, lrs = float(int(self.version) + 1), tuple(self._lrs)
-        xgmi = self._xgmi
-        snap = xgmi is not None and self.defer_host_reads
-        if snap:  # the exchange's status word travels with this step's numbers (a blocking read would wait for the whole queue)
-            vec = torch.cat([vec, xgmi.status_snapshot(torch.empty(1, dtype=torch.float32, device=vec.device))])
 
         def finish(host: list) -> dict:
-            if snap:
-                timed_out, host = host[-1] != 0.0, host[:-1]
-                if timed_out:
-                    xgmi.check_status()  # raises: a peer never published its gradient during this step
             any_counted = host[-1] > 0
             out = {k: host[DPPO_OUT_NAMES[k]] for k in _DECOUPLED_KEYS + _CRITIC_KEYS}
             if has_versions and any_counted:
@@ -440,6 +387,4 @@ class AsyncPPOEmbodiedFSDPActor(EmbodiedFSDPActor):
             out["actor/lr"], out["critic/lr"] = lrs
             return out
 
-        if self.defer_host_reads:
-            return PendingMetrics(vec, finish)
-        return finish(vec.tolist())
+        return self._read_update_metrics(vec, finish)

@@ -70,8 +70,8 @@ class EmbodiedFSDPActor(Worker):
         self.fused_step = bool(a.get("fused_step", True))
         # let the optimizer kernel scatter the new weights into the fragment-tile image (instead of one re-pack launch per step)
         self.optimizer_writes_tiles = bool(a.get("optimizer_writes_tiles", True))
-        self._graph = None
-        self._graph_key = None
+        # the update phase's prepared launches (_update_plan) and their hipGraph (_replay_or_capture), each with the key it was built for
+        self._plan = self._plan_key = self._graph = self._graph_key = None
         self._lr_log: list = []
         # runner.use_training_pipeline (embodied_runner.py:479, env_worker.py:1469-1572, fsdp_actor_worker_pipeline.py): the
         # env side normalises advantages from (count, sum, sumsq) statistics and hands the learner per-stage shuffled
@@ -136,9 +136,12 @@ class EmbodiedFSDPActor(Worker):
         are dropped."""
         self._lrs = self.lr_scheduler.get_last_lr()
         self.groups = self.model.group_ranges(self._lrs[0], self._lrs[1], train_value_head=self.cfg.algorithm.loss_type != "actor")
-        for key in ("prepared_key", "aplan_key", "agraph_key"):  # (the async learner's plan and graph: async_ppo_fsdp_worker.py)
-            self._ws.pop(key, None)
-        self._graph = None
+        self._drop_launches()
+
+    def _drop_launches(self):
+        """The prepared plan and the captured graph hold learning rates by value and the sync words by pointer: when either
+        changes both are built again."""
+        self._plan = self._plan_key = self._graph = self._graph_key = None
 
     def _one_launch_expired(self, grad_norm: float):
         """ops.check_adamw_sync's verdict on an iteration's gradient norm: when the one-launch optimizer step's exchange expired
@@ -147,9 +150,7 @@ class EmbodiedFSDPActor(Worker):
         pointer are dropped."""
         if ops.check_adamw_sync(self.adamw_sync, grad_norm):
             self._retired_adamw_sync, self.adamw_sync = self.adamw_sync, None
-            for key in ("prepared_key", "aplan_key", "agraph_key"):
-                self._ws.pop(key, None)
-            self._graph = None
+            self._drop_launches()
 
     def _step_lr_scheduler(self):
         """lr_scheduler.step() once per run_training (embodied_fsdp_actor_worker.py:568)."""
@@ -476,6 +477,22 @@ class EmbodiedFSDPActor(Worker):
                 bwd_ws=torch.empty(lib.rlx_mlp_bwd_workspace_bytes(ops.byref(lay), mb), dtype=torch.uint8, device=dev))
         return self._ws[key]
 
+    METRIC_ROW_FLOATS = PPO_OUT_FLOATS  # width of one micro-batch's metric row
+
+    def _update_buffers(self, micro: int, accum: int, n_steps: int) -> tuple:
+        """(minibatch workspace, gradient slabs [slabs * accum, n_params], metric rows [n_steps * accum, METRIC_ROW_FLOATS], norm rows
+        [n_steps, 2]) of an update phase -- the same tensors on every call: prepared launches and captured graphs hold their
+        addresses."""
+        ws = self._minibatch_workspace(micro)
+        gkey, mkey = ("grads", micro, accum), ("metrics", n_steps, accum)
+        if gkey not in self._ws:
+            self._ws[gkey] = torch.zeros((ws["slabs"] * accum, self.model.n_params), dtype=torch.float32, device=self.device)
+        if mkey not in self._ws:
+            self._ws[mkey] = (torch.zeros(n_steps * accum, self.METRIC_ROW_FLOATS, device=self.device),
+                              torch.zeros(n_steps, 2, device=self.device))
+        self._grad_out_host = 1.0 / accum
+        return ws, self._ws[gkey], *self._ws[mkey]
+
     def _loss_params(self, critic_warmup: bool):
         alg, m = self.cfg.algorithm, self.cfg.actor.model
         has_critic = alg.loss_type == "actor_critic"
@@ -538,6 +555,20 @@ class EmbodiedFSDPActor(Worker):
         ops.gaussian_entropy_bonus_(self.model.flat.data, self.model.layout, grads[0], out_row, bonus, self._grad_out_host,
                                     has_mask, 1.0 / self.model.layout.act_dim if per_elem else 1.0, actor_scale=actor_scale)
 
+    def _adamw_call(self, grads: torch.Tensor, groups: list, stats: torch.Tensor, deferred: dict | None = None) -> "ops.PreparedAdamw":
+        """One optimizer step's clip + AdamW as a prepared call.  One rank: over the slabs.  xGMI: stage + peer-read reduce + clip
+        + AdamW from this rank's slabs, the mean landing in grad_flat.  RCCL: on grad_flat, which the caller fills (slab sum, with
+        ``deferred`` applied there, + all-reduce) in front of the call."""
+        o, m, multi, xg = self.cfg.actor.optim, self.model, self._exchange, self._xgmi
+        tiles = m.tiles() if (self.fused_step and self.optimizer_writes_tiles) else None
+        return ops.PreparedAdamw(
+            m.flat.data, self.grad_flat if (multi and xg is None) else grads, self.exp_avg, self.exp_avg_sq, groups,
+            betas=(o.adam_beta1, o.adam_beta2), eps=o.adam_eps, weight_decay=o.weight_decay, max_grad_norm=o.clip_grad,
+            grad_scale=1.0 / self._world_size if multi else 1.0, stats=stats, step_state=self.step_state, workspace=self.adamw_ws,
+            tile_layout=m.layout if tiles is not None else None, tiles=tiles, xgmi=xg,
+            grad_flat=self.grad_flat if xg is not None else None, deferred=deferred, deferred_in_caller=multi and xg is None,
+            sync=self.adamw_sync)
+
     def optimizer_step(self, grads: torch.Tensor, stats: torch.Tensor | None = None, critic_warmup: bool = False):
         """clip_grad_norm_ + AdamW (+ data-parallel mean of the gradient) -> stats (norm, applied) on device.  The
         optimizer kernel also refreshes the fragment-tile weight image the next forward (and the rollout) streams.
@@ -550,21 +581,13 @@ class EmbodiedFSDPActor(Worker):
             vh = [(self.model.offsets[n], self.model.offsets[n] + self.model.view(n).numel())
                   for n in self.model.shapes if "value_head" in n]
             groups = [(max(b, vb), min(e, ve), lr) for (b, e, lr) in self.groups for (vb, ve) in vh if max(b, vb) < min(e, ve)]
-        tiles = self.model.tiles() if (self.fused_step and self.optimizer_writes_tiles) else None
-        kw = dict(betas=(o.adam_beta1, o.adam_beta2), eps=o.adam_eps, weight_decay=o.weight_decay, max_grad_norm=o.clip_grad,
-                  stats=self.opt_stats if stats is None else stats, step_state=self.step_state, workspace=self.adamw_ws,
-                  tile_layout=self.model.layout if tiles is not None else None, tiles=tiles, sync=self.adamw_sync)
-        if self._xgmi is not None:  # stage + peer-read reduce + clip + AdamW: three launches, no host round trip
-            ops.PreparedAdamw(self.model.flat.data, grads, self.exp_avg, self.exp_avg_sq, groups, grad_scale=1.0 / self._world_size,
-                              xgmi=self._xgmi, grad_flat=self.grad_flat, **kw)(torch.cuda.current_stream(self.device).cuda_stream)
-        elif self._exchange:
+        adam = self._adamw_call(grads, groups, self.opt_stats if stats is None else stats)
+        if self._exchange and self._xgmi is None:
             ops.sum_slabs(grads, out=self.grad_flat)
             all_reduce_flat_(self.grad_flat, self.ctx)  # RCCL, one flat 1.15 MB buffer (C1)
-            ops.clip_adamw_step_(self.model.flat.data, self.grad_flat, self.exp_avg, self.exp_avg_sq, groups, 0,
-                                 grad_scale=1.0 / self._world_size, **kw)
-        else:
-            ops.clip_adamw_step_(self.model.flat.data, grads, self.exp_avg, self.exp_avg_sq, groups, 0, grad_scale=1.0, **kw)
-        self.model.mark_updated(tiles_fresh=tiles is not None)
+        with torch.cuda.device(self.device):
+            adam(torch.cuda.current_stream(self.device).cuda_stream)
+        self.model.mark_updated(tiles_fresh=self.fused_step and self.optimizer_writes_tiles)
         self.optimizer_steps += 1
         # lr_list of FSDPModelManager.optimizer_step (:451-461): while the critic warms up the optimizer holds ONE group and
         # reports 0.0 for it (-> actor/lr = 0.0, no critic/lr entry for this step), the scheduled rates afterwards
@@ -574,21 +597,17 @@ class EmbodiedFSDPActor(Worker):
             self.critic_warmup_steps = 0
             self._build_lr_scheduler()  # ... and a new scheduler over it (:456-459)
 
-    def _run_update(self, flat: dict, N: int, metrics_dev: torch.Tensor, norms_dev: torch.Tensor):
+    def _run_update(self, flat: dict, N: int) -> int:
         a, alg = self.cfg.actor, self.cfg.algorithm
         n_mb, per_rank, accum = minibatch_plan(N, a.global_batch_size, a.micro_batch_size, self._world_size)
         assert accum == self.gradient_accumulation
         micro = a.micro_batch_size
-        ws = self._minibatch_workspace(micro)
-        key = ("grads", micro, accum)
-        if key not in self._ws:
-            self._ws[key] = torch.zeros((ws["slabs"] * accum, self.model.n_params), dtype=torch.float32, device=self.device)
+        ws, grads, metrics_dev, norms_dev = self._update_buffers(micro, accum, n_mb * alg.get("update_epoch", 1))
+        if "grad_out" not in self._ws:  # (the stage-by-stage loss backward reads its scale from the device)
             self._ws["grad_out"] = torch.full((1,), 1.0 / accum, dtype=torch.float32, device=self.device)
-        grads, grad_out = self._ws[key], self._ws["grad_out"]
-        self._grad_out_host = 1.0 / accum
         if self.fused_step and self.critic_warmup_steps == 0:
-            return self._run_update_prepared(flat, N, metrics_dev, norms_dev, grads, ws, n_mb, per_rank, accum, micro)
-        step = 0
+            return self._exec_plan(self._update_plan(flat, N, n_mb, per_rank, accum), grads)
+        grad_out, step = self._ws["grad_out"], 0
         for _ in range(alg.get("update_epoch", 1)):
             for i in range(n_mb):
                 lp = self._loss_params(self.optimizer_steps < self.critic_warmup_steps)
@@ -604,45 +623,40 @@ class EmbodiedFSDPActor(Worker):
                 step += 1
         return step
 
-    def _run_update_prepared(self, flat, N, metrics_dev, norms_dev, grads, ws, n_mb, per_rank, accum, micro, only_build=False):
-        """The same loop with every launch marshalled once: all buffers are persistent, so an optimizer step is a handful of
-        ctypes calls (+ one torch.distributed all-reduce when world_size > 1) -- the eager path of multi-GPU runs is
-        otherwise bound by Python argument marshalling, not by the GPU."""
-        m, o = self.model, self.cfg.actor.optim
-        epochs = self.cfg.algorithm.get("update_epoch", 1)
-        pkey = ("prepared", N, micro, accum, epochs, tuple(t.data_ptr() for t in flat.values()), metrics_dev.data_ptr())
-        if self._ws.get("prepared_key") != pkey:
-            bf16 = m.compute_dtype == torch.bfloat16
-            tiles = m.tiles() if self.optimizer_writes_tiles else None
-            lp = self._loss_params(False)
-            multi = self._exchange
-            xg = self._xgmi
-            plan, step = [], 0
-            for _ in range(epochs):
-                for i in range(n_mb):
-                    micro_calls = []
-                    for j in range(accum):
-                        lo = i * per_rank + j * micro
-                        mbatch = {k: v[lo:lo + micro] for k, v in flat.items()}
-                        micro_calls.append(ops.PreparedPpoStep(
-                            m.flat.data, m.layout, lp, mbatch, grads[j * ws["slabs"]:(j + 1) * ws["slabs"]],
-                            metrics_dev[step * accum + j], ws["step_ws"], grad_out=self._grad_out_host, tiles=tiles, bf16=bf16))
-                        if float(self.cfg.algorithm.get("entropy_bonus", 0) or 0) > 0:
-                            micro_calls.append(lambda _stream, mb=mbatch, g=grads[j * ws["slabs"]:(j + 1) * ws["slabs"]],
-                                               row=metrics_dev[step * accum + j]: self._entropy_bonus(mb, g, row))
-                    adam = ops.PreparedAdamw(
-                        m.flat.data, self.grad_flat if (multi and xg is None) else grads, self.exp_avg, self.exp_avg_sq, self.groups,
-                        betas=(o.adam_beta1, o.adam_beta2), eps=o.adam_eps, weight_decay=o.weight_decay,
-                        max_grad_norm=o.clip_grad, grad_scale=1.0 / self._world_size if multi else 1.0, stats=norms_dev[step],
-                        step_state=self.step_state, workspace=self.adamw_ws, tile_layout=m.layout if tiles is not None else None,
-                        tiles=tiles, xgmi=xg, grad_flat=self.grad_flat if xg is not None else None, sync=self.adamw_sync)
-                    plan.append((micro_calls, adam))
-                    step += 1
-            self._ws["prepared_key"], self._ws["prepared_plan"] = pkey, plan
-        plan = self._ws["prepared_plan"]
-        if only_build:
-            return plan
-        return self._exec_plan(plan, grads)
+    def _update_plan(self, flat: dict, N: int, n_mb: int, per_rank: int, accum: int) -> list:
+        """The fused update phase with every launch marshalled once: [(micro-batch calls, AdamW call)] per optimizer step, update
+        epochs x global batches (pass-major: entry k * n_mb + g trains global batch g for the (k + 1)-th time).  All buffers are
+        persistent, so an optimizer step is a handful of ctypes calls (+ one torch.distributed all-reduce over RCCL) -- the eager path
+        is otherwise bound by Python argument marshalling, not by the GPU.  What a learner trains is in its two hooks,
+        _micro_batch_calls and _step_deferred; _exec_plan issues the plan."""
+        micro, epochs = int(self.cfg.actor.micro_batch_size), int(self.cfg.algorithm.get("update_epoch", 1))
+        ws, grads, rows, norms = self._update_buffers(micro, accum, n_mb * epochs)
+        key = (N, micro, accum, epochs, tuple((k, t.data_ptr()) for k, t in flat.items()), rows.data_ptr())
+        if self._plan_key != key:
+            lp, slabs, plan = self._loss_params(False), ws["slabs"], []
+            for step in range(n_mb * epochs):
+                calls, step_rows = [], rows[step * accum:(step + 1) * accum]
+                for j in range(accum):
+                    lo = (step % n_mb) * per_rank + j * micro
+                    calls += self._micro_batch_calls(lp, {k: v[lo:lo + micro] for k, v in flat.items()},
+                                                     grads[j * slabs:(j + 1) * slabs], step_rows[j], ws["step_ws"])
+                plan.append((calls, self._adamw_call(grads, self.groups, norms[step], self._step_deferred(step_rows, accum))))
+            self._plan, self._plan_key = plan, key
+        return self._plan
+
+    def _micro_batch_calls(self, lp, mb: dict, g: torch.Tensor, row: torch.Tensor, step_ws: torch.Tensor) -> list:
+        """Plan hook: the prepared calls of one micro-batch -- views ``mb``, gradient slabs ``g``, metric row ``row``."""
+        m = self.model
+        calls = [ops.PreparedPpoStep(m.flat.data, m.layout, lp, mb, g, row, step_ws, grad_out=self._grad_out_host,
+                                     tiles=m.tiles() if self.optimizer_writes_tiles else None,
+                                     bf16=m.compute_dtype == torch.bfloat16)]
+        if float(self.cfg.algorithm.get("entropy_bonus", 0) or 0) > 0:
+            calls.append(lambda _stream: self._entropy_bonus(mb, g, row))
+        return calls
+
+    def _step_deferred(self, step_rows: torch.Tensor, accum: int) -> dict | None:
+        """Plan hook: the ``deferred`` argument of the AdamW call behind the micro-batches whose metric rows are ``step_rows``."""
+        return None
 
     def _exec_plan(self, plan: list, grads: torch.Tensor, lo: int = 0, hi: int | None = None) -> int:
         """Steps [lo, hi) of a prepared plan on the current stream."""
@@ -708,22 +722,9 @@ class EmbodiedFSDPActor(Worker):
         n_mb, per_rank, accum = minibatch_plan(N, a.global_batch_size, a.micro_batch_size, self._world_size)
         assert N_e % per_rank == 0, f"a rollout epoch ({N_e} rows) must hold whole global batches ({per_rank} rows per rank)"
         n_e, epochs = N_e // per_rank, alg.get("update_epoch", 1)
-        key = ("metrics", n_mb * epochs, accum)
-        if key not in self._ws:
-            self._ws[key] = (torch.zeros(n_mb * epochs * accum, PPO_OUT_FLOATS, device=self.device),
-                             torch.zeros(n_mb * epochs, 2, device=self.device))
-        metrics_dev, norms_dev = self._ws[key]
-        micro = a.micro_batch_size
-        ws = self._minibatch_workspace(micro)
-        gkey = ("grads", micro, accum)
-        if gkey not in self._ws:
-            self._ws[gkey] = torch.zeros((ws["slabs"] * accum, self.model.n_params), dtype=torch.float32, device=self.device)
-            self._ws["grad_out"] = torch.full((1,), 1.0 / accum, dtype=torch.float32, device=self.device)
-        grads = self._ws[gkey]
-        self._grad_out_host = 1.0 / accum
+        _, grads, metrics_dev, norms_dev = self._update_buffers(a.micro_batch_size, accum, n_mb * epochs)
         assert self.fused_step and self.critic_warmup_steps == 0, "the pipeline learner runs the fused prepared step"
-        # the plan is laid out pass-major: entry k * n_mb + g trains global batch g for the (k + 1)-th time
-        plan = self._run_update_prepared(bigs[0], N, metrics_dev, norms_dev, grads, ws, n_mb, per_rank, accum, micro, only_build=True)
+        plan = self._update_plan(bigs[0], N, n_mb, per_rank, accum)
         order = self._pipeline_schedule(E, n_e, epochs)
         assert sorted(order) == [(k, g) for k in range(epochs) for g in range(n_mb)], "every (pass, global batch) exactly once"
         prepared, seen, run = {0}, set(), []
@@ -768,16 +769,10 @@ class EmbodiedFSDPActor(Worker):
             flat, N = self._flatten_and_shuffle()
             n_mb, _, accum = minibatch_plan(N, a.global_batch_size, a.micro_batch_size, self._world_size)
             n_steps = n_mb * alg.get("update_epoch", 1)
-            key = ("metrics", n_steps, accum)
-            if key not in self._ws:
-                self._ws[key] = (torch.zeros(n_steps * accum, PPO_OUT_FLOATS, device=self.device),
-                                 torch.zeros(n_steps, 2, device=self.device))
-            metrics_dev, norms_dev = self._ws[key]
+            _, _, metrics_dev, norms_dev = self._update_buffers(a.micro_batch_size, accum, n_steps)
             self._lr_log = []  # (actor lr, critic lr or None) per optimizer step of this call
-            if self.enable_hip_graph and self.critic_warmup_steps == 0 and self.lr_scheduler.is_static and self._capturable():
-                self._replay_or_capture(flat, N, metrics_dev, norms_dev, n_steps)
-            else:
-                self._run_update(flat, N, metrics_dev, norms_dev)
+            self._run_or_replay((N, n_steps, tuple(sorted(flat)), tuple(t.data_ptr() for t in flat.values())),
+                                lambda: self._run_update(flat, N), n_steps)
             if self.use_training_pipeline:
                 Tb, Bb = self.rollout_batch["prev_logprobs"].shape[:2]
                 self._prefetch_pipeline_perms(Tb, Bb, 1)  # host work for the NEXT iteration, behind the enqueued update phase
@@ -796,19 +791,25 @@ class EmbodiedFSDPActor(Worker):
         import torch.distributed as dist
         return dist.get_backend() == "nccl"
 
-    def _replay_or_capture(self, flat, N, metrics_dev, norms_dev, n_steps):
+    def _run_or_replay(self, key, run, n_steps: int):
+        """``run()`` -- the update phase, ``n_steps`` optimizer steps -- as is, or through its hipGraph where it can live in one."""
+        if self.enable_hip_graph and self.critic_warmup_steps == 0 and self.lr_scheduler.is_static and self._capturable():
+            self._replay_or_capture(key, run, n_steps)
+        else:
+            run()
+
+    def _replay_or_capture(self, key, run, n_steps: int):
         """hipGraph of the whole update phase (all epochs x minibatches): every buffer is persistent and the step
-        counter lives on the device, so the captured launch chain can be replayed as is."""
-        gkey = (N, n_steps, tuple(sorted(flat)), tuple(t.data_ptr() for t in flat.values()))
-        if self._graph is None or self._graph_key != gkey:
-            self._run_update(flat, N, metrics_dev, norms_dev)  # real run; also warms every workspace
+        counter lives on the device, so the captured launch chain can be replayed as is.  ``key``: what the chain depends on."""
+        if self._graph is None or self._graph_key != key:
+            run()  # real run; also warms every workspace
             torch.cuda.synchronize(self.device)
             steps_before = self.optimizer_steps
             g = torch.cuda.CUDAGraph()
             ok = 1
             try:
                 with torch.cuda.graph(g):
-                    self._run_update(flat, N, metrics_dev, norms_dev)
+                    run()
             except Exception as e:  # noqa: BLE001 -- e.g. an RCCL build that cannot be stream-captured
                 if not self._exchange:
                     raise
@@ -824,7 +825,7 @@ class EmbodiedFSDPActor(Worker):
             if not ok:
                 self.enable_hip_graph = False
                 return
-            self._graph, self._graph_key = g, gkey
+            self._graph, self._graph_key = g, key
             return
         self._graph.replay()
         # the raw-pointer kernels do not bump flat._version: tell the model which derived images are stale now (the tile
@@ -848,17 +849,8 @@ class EmbodiedFSDPActor(Worker):
         # averaged per optimizer step like every other entry of the reference's metric lists (append_to_dict + np.mean);
         # a replayed graph ran every step at the current rates and logs nothing per step
         log = list(self._lr_log) or [(self._lrs[0], self._lrs[1])]
-        xgmi = self._xgmi
-        snap = xgmi is not None and self.defer_host_reads
-        if snap:  # the exchange's status word rides along with THIS step's numbers (a blocking read here would wait for the whole queue,
-            #       and one iteration late it would report -- and clear -- the NEXT step's time-out)
-            vec = torch.cat([vec, xgmi.status_snapshot(torch.empty(1, dtype=torch.float32, device=vec.device))])
 
         def finish(host: list) -> dict:
-            if snap:
-                timed_out, host = host[-1] != 0.0, host[:-1]
-                if timed_out:
-                    xgmi.check_status()  # raises (and clears the word): a peer never published its gradient during this step
             out = {k: host[PPO_OUT_NAMES[k]] for k in _ACTOR_KEYS}
             if has_critic:
                 out.update({k: host[PPO_OUT_NAMES[k]] for k in _CRITIC_KEYS})
@@ -874,6 +866,22 @@ class EmbodiedFSDPActor(Worker):
                 out["critic/lr"] = float(np.mean(critic))
             return out
 
-        if self.defer_host_reads:  # the runner reads one iteration late (utils/pending.py)
+        return self._read_update_metrics(vec, finish)
+
+    def _read_update_metrics(self, vec: torch.Tensor, finish):
+        """``finish(vec as a host list)`` now, or as PendingMetrics when the runner reads one iteration late (utils/pending.py).
+        Read late over xGMI, the exchange's status word rides along with THIS step's numbers (a blocking read here would wait
+        for the whole queue, and one iteration late it would report -- and clear -- the NEXT step's time-out)."""
+        xgmi = self._xgmi
+        if not self.defer_host_reads:
+            return finish(vec.tolist())
+        if xgmi is None:
             return PendingMetrics(vec, finish)
-        return finish(vec.tolist())
+        vec = torch.cat([vec, xgmi.status_snapshot(torch.empty(1, dtype=torch.float32, device=vec.device))])
+
+        def checked(host: list) -> dict:
+            if host[-1] != 0.0:
+                xgmi.check_status()  # raises (and clears the word): a peer never published its gradient during this step
+            return finish(host[:-1])
+
+        return PendingMetrics(vec, checked)

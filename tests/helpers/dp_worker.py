@@ -204,7 +204,7 @@ def gpu_async_main(out_path, precision, transport="xgmi", graph="0", backend="gl
     w.rollout_batch["versions"][T // 2:] += 1.0
     metrics = w.run_training()
     torch.save(dict(rank=ctx.rank, first_params=first, final_params=w.model.flat.detach().cpu(), metrics=metrics,
-                    backend=w.grad_allreduce_backend, fused="aplan_key" in w._ws, graph="agraph" in w._ws), out_path)
+                    backend=w.grad_allreduce_backend, fused=w._plan is not None, graph=w._graph is not None), out_path)
     dist.barrier()
     dist.destroy_process_group()
 

@@ -131,7 +131,7 @@ def test_store_rounds_match_the_oracle_on_the_stored_trajectories(precision, hip
             failures.append((it, "weights share", float((diff > 2e-5 * (it + 1)).float().mean()), 0.02))
     assert mixed >= 1, "no trained batch held two distinct versions"
     assert mixed == 3, "weight_sync_interval 2 with a store of 2: every round after the first is mixed"
-    assert "aplan_key" in w._ws and (("agraph" in w._ws) == hip_graph), "which learner loop ran"
+    assert w._plan is not None and ((w._graph is not None) == hip_graph), "which learner loop ran"
     runner.close()
     assert not failures, failures
 
