@@ -4,16 +4,27 @@
 //   torch.nn.utils.clip_grad_norm_ (strategy/fsdp.py:363-369, the all-NO_SHARD branch)
 //   + torch.optim.AdamW.step with the actor / value_head parameter groups (fsdp_model_manager.py:501-590),
 //   including "skip the step when the norm is non-finite".
-// Two launches per optimizer step: (1) sum the split-K gradient slabs, scale, write the reduced gradient
-// and per-block sum-of-squares partials (one thread also forms the step's scalars in double); (2) every block
-// re-reduces the (<= 1024) partials, derives the clip coefficient and applies clip + AdamW to its float4 slice.  HBM-bound: 28 B per parameter (+4 B per extra
-// gradient slab); at 287 504 parameters it is launch-latency bound, which is why it is only two launches.
-// (A single persistent launch around a device-wide barrier was measured: 33-49 us against 7 + 11 us here -- on an 8-XCD part
-// the arrivals are serialised same-address device-scope atomics and every poll crosses to the memory-side coherence point.)
+// Three shapes of the step, chosen by the entry points from what the caller hands over:
+//   two launches          (1) sum the split-K gradient slabs, scale, write the reduced gradient and per-block sum-of-squares
+//                         partials (one thread also forms the step's scalars in double); (2) every block re-reduces the (<= 1024)
+//                         partials, derives the clip coefficient and applies clip + AdamW to its float4 slice.  HBM-bound: 28 B per
+//                         parameter (+4 B per extra gradient slab); at 287 504 parameters it is launch-latency bound.
+//   one launch            (rlx_adamw_params.sync_words) slab sum + norm partial, an exchange of the partials as self-validating 64-bit
+//                         words in per-block slots, clip + AdamW on the gradient still in registers; blocks dealt out by SegPlan so that
+//                         a block holds eight whole rows of a hidden matrix.  With world_size > 1 the gradient exchange over xGMI rides
+//                         in the same kernel (pushed words, polled locally).  See the comment above XchgPeers.
+//   multi-rank chains     peer hand-shake (in the reduce launch or as peer_wait_kernel), reduce(-scatter), gather + clip + AdamW
+//                         (opt_common.h: PeerWait, ReduceSrc, GatherSrc).
+// (A single persistent launch around a device-wide barrier was measured: 33-49 us against 7 + 11 us for the two launches -- on an 8-XCD
+// part the arrivals are serialised same-address device-scope atomics and every poll crosses to the memory-side coherence point; the
+// one-launch shape has no counter.)
+// Every shape keeps the MLP's fragment-tile weight image current when the caller passes one (tile_scatter / apply_seg_block), in the
+// format of the process's step::Form (ppo_step_form.h; resolved on the host by tile_format_resolved).
 
 #include <algorithm>
 
 #include "opt_common.h"
+#include "ppo_step_form.h"
 
 namespace rlx {
 namespace {
@@ -195,7 +206,7 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherSrc src, float* __res
         reinterpret_cast<float4*>(out)[i] = gather_f4(src, off, i);
 }
 
-// Fragment-tile weight image (ppo_step.hip, struct Tiles) kept in step with the flat parameters: the optimizer writes
+// Fragment-tile weight image (ppo_step_common.h, struct Tiles) kept in step with the flat parameters: the optimizer writes
 // every updated weight to its tile slot(s) as well, so no separate re-pack launch is needed before the next forward.
 __device__ __forceinline__ size_t tile_slot(size_t mat_off, int nit, int n, int k) {  // f32 tiles: 16 (n) x 16 (k), two per 32 k
     return mat_off + ((((size_t)(n >> 4) * nit + (k >> 5)) * 2 + ((k >> 4) & 1)) * 64 + ((k >> 2) & 3) * 16 + (n & 15)) * 4 + (k & 3);
@@ -247,6 +258,12 @@ __device__ __forceinline__ void tile_scatter(const rlx_mlp_layout& lay, float* _
             }
         }
     }
+}
+// the scatter for the image format the host resolved (tile_format_resolved: a step::Form)
+__device__ __forceinline__ void tile_scatter_as(int form, const rlx_mlp_layout& lay, float* __restrict__ tiles, long long i, float val) {
+    if (form == (int)step::Form::BF16) tile_scatter<(int)step::Form::BF16>(lay, tiles, i, val);
+    else if (form == (int)step::Form::F32X) tile_scatter<(int)step::Form::F32X>(lay, tiles, i, val);
+    else tile_scatter<(int)step::Form::F32>(lay, tiles, i, val);
 }
 
 // beta ** step for an integer step by repeated squaring: <= 2 log2(step) double multiplications (each within half an ulp; the
@@ -344,9 +361,7 @@ __device__ __forceinline__ void scatter_tiles_f4(long long iw, int lane, const f
             const int gq = c == 0 ? q0 : (c == 1 ? q1 : (c == 2 ? q2 : q3));
             if (skip || gq < 0) continue;
             const long long idx = 4 * iw + 64 * e + lane;
-            if (a.tiles_bf16 == 1) tile_scatter<1>(lay, tiles, idx, val);
-            else if (a.tiles_bf16 == 2) tile_scatter<2>(lay, tiles, idx, val);
-            else tile_scatter<0>(lay, tiles, idx, val);
+            tile_scatter_as(a.tiles_bf16, lay, tiles, idx, val);
         }
     }
 }
@@ -552,11 +567,7 @@ __global__ __launch_bounds__(256) void clip_adamw_kernel(float* __restrict__ p, 
         p[i] = pi;
         m[i] = mi;
         v[i] = vi;
-        if (tiles != nullptr) {
-            if (a.tiles_bf16 == 1) tile_scatter<1>(lay, tiles, i, pi);
-            else if (a.tiles_bf16 == 2) tile_scatter<2>(lay, tiles, i, pi);
-            else tile_scatter<0>(lay, tiles, i, pi);
-        }
+        if (tiles != nullptr) tile_scatter_as(a.tiles_bf16, lay, tiles, i, pi);
     }
 }
 
@@ -1021,10 +1032,6 @@ __global__ void seq_inc_kernel(unsigned* seq) { *seq += 1u; }
 
 }  // namespace
 
-namespace step {
-bool f32_split();  // ppo_step_f32x.hip
-}
-
 namespace opt {
 
 int check_deferred(const rlx_adamw_params* p, int nslab, int64_t n, const char* who) {
@@ -1041,11 +1048,11 @@ int grid_for(long long n) {  // one float4 per thread up to kMaxParts blocks, gr
 }
 
 namespace {
-// The kernel's copy of the parameters with the tile image's format resolved: an f32 image (tiles_bf16 == 0) is the three-plane one
-// unless the process runs the exact-f32-MFMA launches (RLX_F32_EXACT_MFMA=1) -- the same switch rlx_mlp_pack_tiles follows.
+// The kernel's copy of the parameters with the tile image's format resolved to a step::Form: an f32 image (tiles_bf16 == 0) is the
+// one the process's f32 launches read -- the same switch rlx_mlp_pack_tiles follows.
 rlx_adamw_params tile_format_resolved(const rlx_adamw_params* p, const float* tiles) {
     rlx_adamw_params k = *p;
-    if (tiles != nullptr && k.tiles_bf16 == 0 && ::rlx::step::f32_split()) k.tiles_bf16 = 2;
+    if (tiles != nullptr && k.tiles_bf16 == 0) k.tiles_bf16 = (int)step::form_of(false);
     return k;
 }
 // Compute units a stream may dispatch to: hipExtStreamCreateWithCUMask streams (utils/streams.py) see a subset, and the

@@ -1,5 +1,5 @@
 // ppo_loss_math.h -- per-element arithmetic of the PPO actor / critic loss and its finalisation, shared by the
-// stand-alone loss kernels (ppo_loss.hip) and the fused optimizer-step kernels (ppo_step.hip).
+// stand-alone loss kernels (ppo_loss.hip) and the fused optimizer-step kernels (ppo_step_*.hip).
 //   compute_ppo_actor_loss   rlinf/algorithms/losses.py:170-312
 //   compute_ppo_critic_loss  rlinf/algorithms/losses.py:315-380  (+ huber_loss rlinf/algorithms/utils.py:20-23,
 //   masked_mean / masked_mean_ratio rlinf/utils/utils.py:323-356, explained-variance stats metric_utils.py:232-258)

@@ -4,7 +4,7 @@
 // fsdp_model_manager.py:122-142, examples/embodiment/config/maniskill_ppo_mlp.yaml:98,128-131): master weights, biases,
 // heads, log-probs, losses, GAE and the optimizer stay f32; only the operands of the 256-wide dense layers are bf16,
 // accumulated in f32 by v_mfma_f32_16x16x32_bf16 (one instruction per 16x16 tile and 32 k: 1/16 of the f32 MFMA time).
-// Same decomposition as ppo_step.hip; what changes with the element size:
+// Same decomposition as ppo_step_f32.hip; what changes with the element size:
 //   * the activation slab lives in LDS as bf16 (row stride 272 elements: conflict-free 16-byte fragment reads);
 //   * weight tiles are 16 (n) x 32 (k) bf16 = 1 KiB, a fragment load is ONE coalesced b128 per lane;
 //   * activations / pre-activation gradients leave the fused kernel as bf16 in a k-tiled TRANSPOSED layout
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(512, 4) void ppo_step_fused_bf16_kernel(StepArgs a,
     gemm.run(Xb, acc);
     epilogue_tanh_b<RT, NW, true>(acc, sBias + 2 * HID, Xb, kept3, nullptr, tg.nrb, m0);
 
-    // ---- head + loss element math (f32, identical to ppo_step.hip): fused_loss_pass, ppo_step_bf16_parts.h -------------------------
+    // ---- head + loss element math (f32, identical to ppo_step_f32.hip): fused_loss_pass, ppo_step_bf16_parts.h ---------------------
     head_forward_mfma<RT>(Xb, W4s, sG, sLp);  // the two k-half partials land in sG / sLp (both free until the passes below)
     lds_barrier();
     fused_loss_pass<BM, NW, DEC>(a, y, tile, m0, LossLds{b4s, sHead, sLp, sG, sD, sOld, sAct, sAdv, sRet, sStd, reinterpret_cast<double*>(Xb), sNm});
@@ -950,6 +950,8 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
 }  // namespace
 
 namespace step {
+
+size_t tiles_bytes_bf16() { return 2 * Tiles::per_net() * sizeof(__bf16); }
 
 int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st) {
     hipLaunchKernelGGL(pack_tiles_bf16_kernel, dim3(num_cu() * 4), dim3(256), 0, st, params, lay, static_cast<__bf16*>(tiles));

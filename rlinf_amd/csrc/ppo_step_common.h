@@ -1,5 +1,6 @@
-// ppo_step_common.h -- pieces shared by the f32 (ppo_step.hip) and bf16 (ppo_step_bf16.hip) fused launches:
-// geometry, LDS barrier, fast tanh, kernel argument structs, host-side planning.
+// ppo_step_common.h -- pieces shared by the three precision forms of the fused launches (ppo_step_f32.hip, ppo_step_bf16.hip,
+// ppo_step_f32x.hip) and their entry points (ppo_step.hip): geometry, LDS barrier, fast tanh, kernel argument structs, the table of
+// the forms' launchers, host-side planning.
 #pragma once
 
 #include <stdlib.h>
@@ -7,6 +8,7 @@
 #include <algorithm>
 
 #include "ppo_loss_math.h"
+#include "ppo_step_form.h"
 #include "rlx_common.h"
 
 namespace rlx {
@@ -345,37 +347,53 @@ struct StepPlan {
     int slabs, rows_per_slab, head_stride;
     size_t off_h, off_dz, off_head, off_loss, off_tiles, off_st, bytes;
 };
-constexpr int STEP_BM = 64;
-// precision "32": true (default) = the f32 launches run on the bf16 matrix pipe with three-plane operands (ppo_step_f32x.hip),
-// false (RLX_F32_EXACT_MFMA=1, read once per process) = the exact-f32-MFMA launches of ppo_step.hip.  The f32 weight image
-// (rlx_mlp_pack_tiles / the optimizer's tile refresh) follows the same switch.
-bool f32_split();
-size_t f32x_tiles_bytes();
+constexpr int STEP_BM = 64;  // rows per workgroup of the exact-f32 fused launch
+
+// The launchers of one form; every form file (ppo_step_f32.hip, ppo_step_bf16.hip, ppo_step_f32x.hip) exposes the same four.
+struct FormOps {
+    size_t (*tiles_bytes)();  // the form's weight image
+    int (*pack)(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
+    int (*launch_rollout)(const RolloutArgs& a, int blocks, hipStream_t st);
+    // st_tiles: the states' k-tiled image in the workspace (StepPlan.off_st; unused by F32); tiles: StepPlan.tiles
+    int (*launch_step)(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st);
+};
+const FormOps& ops_of(Form f);  // ppo_step.hip
+
 // rows per workgroup of the bf16 fused launch: 32 (two workgroups per CU at 8192 rows -- their phases, matrix pipe / VALU
 // epilogues / barrier and memory latency, overlap; 58 KB of LDS and 128 VGPRs each).  64 (one per CU, half the weight-fragment
 // traffic, 157 KB of LDS) measured 27.7 against 25.6 us and was removed (profiles/r02_fused_rows_per_workgroup.txt).
 // rows per workgroup of the f32x fused launch: 32 (the three-plane slab allows one workgroup per CU either way; 64 rows -- half the
 // weight bytes per row, ONE round of 256 workgroups at 8192 rows -- measured the same 82 us and was removed, profiles/r05_f32x_*)
-inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = false) {
+inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, Form form) {
     StepPlan pl{};
-    const bool f32x = !bf16 && f32_split();
-    const int bm = bf16 || f32x ? 32 : STEP_BM;
+    const int bm = form == Form::F32 ? STEP_BM : 32;
     pl.tiles = ceil_div(m, bm);
     pl.head_parts = pl.tiles * (bm / 32);
     pl.loss_slots = pl.tiles;
-    // 20 GEMM items per slab.  Every slab is 1.15 MB written here and read back by the slab reduce through the memory side:
-    // (round 2, the LDS-DMA kernel with the copies in the compute waves: 16 slabs = 1.25 workgroups per CU was its best trade --
-    // 16.2 us + slab reduce 9.1 us, against 15.8 + 10.4 us with 24 slabs)
-    // (the exact-f32 launch is bound by the f32 matrix pipe, not by slab bytes: it keeps 2 workgroups per CU in one round --
-    //  measured 71 us with 24 slabs against 97 us with 16)
-    // bf16, round 4 (ring weight-gradient launch: loader waves, one 64 KiB workgroup per CU): every workgroup of the launch -- 20 GEMM
-    // items + 2 head-reduce blocks per slab + 1 -- resident at once, NONE sharing a CU: 10 slabs on 256 CUs.  Measured on one box
-    // (profiles/r04_dw_ring_slab_sweep.txt): 16 slabs 19.9 us (353 blocks: a CU with two of them sets the launch's duration),
-    // 12: 21.8 (265 blocks), 11: 15.6, 10: 15.6, 9: 16.4, 8: 17.2 -- against 16.8 for the previous kernel at its best (16 slabs);
-    // the slab reduce behind it 8.84 -> 8.16 us with 10.
-    // f32 through bf16 planes: the loader-wave ring at every size (144 KiB of LDS: one workgroup per CU) -> the same 10-slab plan
-    int want = bf16 ? (m >= 4096 ? std::max(1, (num_cu() - 1) / 25) : 5 * num_cu() / (4 * 20))   // (below 4096 rows: the previous kernel and its plan)
-                    : f32x ? std::max(1, (num_cu() - 1) / 25) : 2 * num_cu() / 20;
+    // 20 GEMM items per slab.  Every slab is 1.15 MB written here and read back by the slab reduce through the memory side.
+    // The ring weight-gradient launches (loader waves, one workgroup per CU) want every workgroup of the launch -- 20 GEMM items + 2
+    // head-reduce blocks per slab + 1 -- resident at once, NONE sharing a CU: 10 slabs on 256 CUs.
+    const int ring = std::max(1, (num_cu() - 1) / 25);
+    int want = 0;
+    switch (form) {
+    case Form::F32:
+        // the exact-f32 launch is bound by the f32 matrix pipe, not by slab bytes: it keeps 2 workgroups per CU in one round --
+        // measured 71 us with 24 slabs against 97 us with 16
+        want = 2 * num_cu() / 20;
+        break;
+    case Form::BF16:
+        // round 4 (ring launch, one 64 KiB workgroup per CU), measured on one box (profiles/r04_dw_ring_slab_sweep.txt): 16 slabs
+        // 19.9 us (353 blocks: a CU with two of them sets the launch's duration), 12: 21.8 (265 blocks), 11: 15.6, 10: 15.6, 9: 16.4,
+        // 8: 17.2 -- against 16.8 for the previous kernel at its best (16 slabs); the slab reduce behind it 8.84 -> 8.16 us with 10.
+        // Below 4096 rows: the previous kernel and its plan (round 2, the LDS-DMA kernel with the copies in the compute waves: 16 slabs
+        // = 1.25 workgroups per CU was its best trade -- 16.2 us + slab reduce 9.1 us, against 15.8 + 10.4 us with 24 slabs).
+        want = m >= 4096 ? ring : 5 * num_cu() / (4 * 20);
+        break;
+    case Form::F32X:
+        // the loader-wave ring at every size (144 KiB of LDS: one workgroup per CU) -> the same 10-slab plan
+        want = ring;
+        break;
+    }
     // ... and at least 256 rows (8 k-blocks) per slab: a data-parallel rank's small minibatch should not pay 16 slabs of traffic
     int slabs = std::max(1, std::min(want, ceil_div(m, 256)));
     pl.rows_per_slab = round_up(ceil_div(m, slabs), 32);
@@ -383,38 +401,41 @@ inline StepPlan plan_step(const rlx_mlp_layout* lay, int64_t m, bool bf16 = fals
     pl.head_stride = head_stride_of(lay);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    if (bf16) {  // k-tiled transposed bf16 images: 16 column blocks x ceil(m / 32) row blocks x 1 KiB per [m][256] matrix
-        const size_t img = (size_t)16 * ceil_div(m, 32) * 1024;
-        pl.off_h = take(4 * img);
-        pl.off_dz = take(6 * img);
-        pl.off_st = take(img / 4);  // states: 4 column blocks
-        pl.off_tiles = take(2 * Tiles::per_net() * 2);
-    } else if (f32x) {  // three planes of every k-tiled image
-        const size_t img = (size_t)16 * ceil_div(m, 32) * 1024;
-        pl.off_h = take(3 * 4 * img);
-        pl.off_dz = take(3 * 6 * img);
-        pl.off_st = take(3 * img / 4);
-        pl.off_tiles = take(f32x_tiles_bytes());
-    } else {
-        pl.off_h = take((size_t)4 * m * HID * sizeof(float));
-        pl.off_dz = take((size_t)6 * m * HID * sizeof(float));
-        pl.off_st = off;
-        pl.off_tiles = take(2 * Tiles::per_net() * sizeof(float));
+    // bf16 / f32x: k-tiled transposed bf16 images, 16 column blocks x ceil(m / 32) row blocks x 1 KiB per [m][256] matrix (the states:
+    // 4 column blocks); f32x keeps three planes of every image.  f32: row-major f32 activations, the weight gradients read the states
+    // themselves.
+    const size_t img = (size_t)16 * ceil_div(m, 32) * 1024;
+    size_t h = 0, dz = 0, stt = 0;
+    switch (form) {
+    case Form::F32: h = (size_t)4 * m * HID * sizeof(float); dz = (size_t)6 * m * HID * sizeof(float); break;
+    case Form::BF16: h = 4 * img; dz = 6 * img; stt = img / 4; break;
+    case Form::F32X: h = 3 * 4 * img; dz = 3 * 6 * img; stt = 3 * img / 4; break;
     }
+    pl.off_h = take(h);
+    pl.off_dz = take(dz);
+    pl.off_st = take(stt);
+    pl.off_tiles = take(ops_of(form).tiles_bytes());
     pl.off_head = take((size_t)pl.head_parts * 2 * pl.head_stride * sizeof(float));
     pl.off_loss = take((size_t)pl.loss_slots * 2 * NS * sizeof(double));
     pl.bytes = off;
     return pl;
 }
 
-// bf16 launches (ppo_step_bf16.hip)
+// exact-f32 MFMA (ppo_step_f32.hip)
+size_t tiles_bytes_f32();
+int pack_tiles_f32(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
+int launch_rollout_f32(const RolloutArgs& a, int blocks, hipStream_t st);
+int launch_step_f32(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st);
+// bf16 (ppo_step_bf16.hip)
+size_t tiles_bytes_bf16();
 int pack_tiles_bf16(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
 int launch_rollout_bf16(const RolloutArgs& a, int blocks, hipStream_t st);
-int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles32, int dw_blocks, hipStream_t st);
+int launch_step_bf16(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st);
 // f32 on the bf16 matrix pipe (ppo_step_f32x.hip)
+size_t tiles_bytes_f32x();
 int pack_tiles_f32x(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st);
 int launch_rollout_f32x(const RolloutArgs& a, int blocks, hipStream_t st);
-int launch_step_f32x(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles32, int dw_blocks, hipStream_t st);
+int launch_step_f32x(const StepArgs& a, const DwArgs& d, void* st_tiles, int tiles, int dw_blocks, hipStream_t st);
 
 }  // namespace step
 }  // namespace rlx

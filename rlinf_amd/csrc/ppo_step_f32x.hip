@@ -1,7 +1,7 @@
 // ppo_step_f32x.hip -- precision "32" (the precision the reference's YAML ships: examples/embodiment/config/model/mlp_policy.yaml:11,
 // maniskill_ppo_mlp.yaml:98,128-131; rlinf/hybrid_engines/fsdp/fsdp_model_manager.py:122-142) on the bf16 matrix pipe, gfx950.
 //
-// The f32 MFMA rate of this part is 1/16 of its bf16 rate, and the round-1 f32 launches (ppo_step.hip: 64-row tiles, 105 KB of LDS,
+// The f32 MFMA rate of this part is 1/16 of its bf16 rate, and the round-1 f32 launches (ppo_step_f32.hip: 64-row tiles, 105 KB of LDS,
 // v_mfma_f32_16x16x4_f32) ran at 113 + 57 us per optimizer step against 26 + 16 us in bf16 mode.  Here every f32 operand travels as
 // THREE bf16 planes
 //        x = hi + mid + lo,   hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)        (3 x 8 significand bits: exact)
@@ -20,7 +20,7 @@
 //   ppo_step_dw_f32x_kernel     weight gradients: loader-wave LDS ring of 48 KiB k-blocks (16 tiles x 3 planes), 4 compute waves
 // Replaces MLPPolicy.default_forward (mlp_policy.py:202-236), compute_ppo_actor_loss / compute_ppo_critic_loss (losses.py:170-380),
 // EmbodiedFSDPActor.train_micro_batch (embodied_fsdp_actor_worker.py:591-700) at precision "32".  RLX_F32_EXACT_MFMA=1 selects the
-// exact-f32-MFMA launches of ppo_step.hip instead (read once per process).
+// exact-f32-MFMA launches of ppo_step_f32.hip instead (read once per process).
 
 #include "ppo_step_bf16_parts.h"
 
@@ -263,7 +263,7 @@ struct StatesX {
     }
 };
 
-// forward hidden-layer epilogue: h = tanh(acc + bias) (f32: the polynomial / exp form of ppo_step.hip) -> three slab planes;
+// forward hidden-layer epilogue: h = tanh(acc + bias) (f32: the polynomial / exp form of ppo_step_f32.hip) -> three slab planes;
 // hp (optional): the planes in the accumulator layout; dst (optional): the k-tiled images (plane stride img_plane) -- which the
 // backward sweep also reads back for 1 - h^2.
 template <int RT, int NW>
@@ -793,12 +793,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
 
 namespace step {
 
-bool f32_split() {  // read once per process
-    static const bool split = !(getenv("RLX_F32_EXACT_MFMA") != nullptr && atoi(getenv("RLX_F32_EXACT_MFMA")) != 0);
-    return split;
-}
-
-size_t f32x_tiles_bytes() { return NPL * TILE_PLANE * sizeof(__bf16); }
+size_t tiles_bytes_f32x() { return NPL * TILE_PLANE * sizeof(__bf16); }
 
 int pack_tiles_f32x(const float* params, const rlx_mlp_layout& lay, void* tiles, hipStream_t st) {
     hipLaunchKernelGGL(pack_tiles_f32x_kernel, dim3(num_cu() * 4), dim3(256), 0, st, params, lay, static_cast<__bf16*>(tiles));
