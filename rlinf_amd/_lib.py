@@ -9,7 +9,9 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RLX_LIB_TAG=<tag>: load librlx_hip_<tag>.so, another build of the same sources (see csrc/build.py) for same-box A/B runs
@@ -59,6 +61,8 @@ class VersionStats(Structure):  # include/rlx.h: rlx_version_stats_out (a device
 
 class SegField(Structure):  # include/rlx.h: rlx_seg_field
     _fields_ = [("srcs", POINTER(c_void_p)), ("dst", c_void_p), ("row_bytes", c_int64), ("t_rows", c_int64)]
+
+
 ADAMW_MAX_GROUPS = 8
 
 
@@ -318,21 +322,15 @@ def load() -> ctypes.CDLL:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents
-    sizes = (c_size_t * len(mirrors))()
-    if lib.rlx_abi_struct_sizes(ctypes.cast(sizes, c_void_p), len(mirrors)) != len(mirrors):
-        raise RlxError("librlx_hip.so and rlinf_amd/_lib.py disagree on the number of argument structs; rebuild the library")
-    for cls, size in zip(mirrors, sizes):
-        if ctypes.sizeof(cls) != size:
-            raise RlxError(f"{cls.__name__}: the ctypes mirror is {ctypes.sizeof(cls)} bytes, the library's struct {size}; "
-                           "rebuild librlx_hip.so (python -m rlinf_amd.csrc.build)")
     later = (VersionStats, SegField)  # the order rlx_abi_struct_sizes_ext documents
-    sizes = (c_size_t * len(later))()
-    if lib.rlx_abi_struct_sizes_ext(ctypes.cast(sizes, c_void_p), len(later)) != len(later):
-        raise RlxError("librlx_hip.so and rlinf_amd/_lib.py disagree on the number of later argument structs; rebuild the library")
-    for cls, size in zip(later, sizes):
-        if ctypes.sizeof(cls) != size:
-            raise RlxError(f"{cls.__name__}: the ctypes mirror is {ctypes.sizeof(cls)} bytes, the library's struct {size}; "
-                           "rebuild librlx_hip.so (python -m rlinf_amd.csrc.build)")
+    for query, classes, which in ((lib.rlx_abi_struct_sizes, mirrors, ""), (lib.rlx_abi_struct_sizes_ext, later, "later ")):
+        sizes = (c_size_t * len(classes))()
+        if query(ctypes.cast(sizes, c_void_p), len(classes)) != len(classes):
+            raise RlxError(f"librlx_hip.so and rlinf_amd/_lib.py disagree on the number of {which}argument structs; rebuild the library")
+        for cls, size in zip(classes, sizes):
+            if ctypes.sizeof(cls) != size:
+                raise RlxError(f"{cls.__name__}: the ctypes mirror is {ctypes.sizeof(cls)} bytes, the library's struct {size}; "
+                               "rebuild librlx_hip.so (python -m rlinf_amd.csrc.build)")
     _lib = lib
     return lib
 
@@ -341,3 +339,16 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().rlx_last_error()
         raise RlxError(f"{what} failed with code {rc}: {msg.decode() if msg else ''}")
+
+
+def launch(name: str, dev, *args, stream: int | None = None) -> None:
+    """The library's ``name(*args, stream)`` with ``dev`` current: a tensor goes as its data pointer (None as NULL), an argument struct by
+    reference, anything else as it is.  ``stream=None``: the current stream of ``dev``, read now.  Raises like ``check``."""
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else byref(a) if isinstance(a, Structure) else a for a in args]
+    with torch.cuda.device(dev):
+        rc = getattr(load(), name)(*argv, torch.cuda.current_stream(dev).cuda_stream if stream is None else stream)
+    check(rc, name)
+
+
+def workspace(dev, nbytes: int) -> torch.Tensor:
+    return torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)

@@ -20,7 +20,6 @@ import torch
 
 from ... import _lib
 from ..._lib import RlxError
-from ...ops import _stream_ptr
 from .patch_syncer import _dtype_code
 
 _STR_DTYPES = {"float32": torch.float32, "fp32": torch.float32, "float16": torch.float16, "fp16": torch.float16,
@@ -129,8 +128,7 @@ def _place_table(table: np.ndarray, dev: torch.device) -> tuple:
 
 def _launch_placed(placed: tuple, dev: torch.device) -> None:
     table_dev, n, chunks = placed
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_copy_segments(table_dev.data_ptr(), n, chunks, _stream_ptr(dev)), "rlx_copy_segments")
+    _lib.launch("rlx_copy_segments", dev, table_dev, n, chunks)
     table_dev.record_stream(torch.cuda.current_stream(dev))
 
 

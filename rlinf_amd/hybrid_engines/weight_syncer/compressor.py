@@ -22,7 +22,6 @@ import torch
 
 from ... import _lib
 from ..._lib import RlxError
-from ...ops import _stream_ptr
 
 # compressor.py:35-46 (the codes travel in the payload: they are part of the wire contract)
 DTYPE_TO_CODE = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3, torch.float16: 4, torch.bfloat16: 5,
@@ -99,11 +98,9 @@ class ZPlaneCompressor(PatchCompressor):
         if t.data_ptr() % 16:
             t = t.clone()
         out = torch.empty(self._lib.rlx_zplane_bound_bytes(n, es), dtype=torch.uint8, device=dev)
-        ws = torch.empty(self._lib.rlx_zplane_workspace_bytes(n, es), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(dev, self._lib.rlx_zplane_workspace_bytes(n, es))
         length = torch.zeros(1, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.rlx_zplane_compress(t.data_ptr(), n, es, out.data_ptr(), out.numel(), length.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "rlx_zplane_compress")
+        _lib.launch("rlx_zplane_compress", dev, t, n, es, out, out.numel(), length, ws, ws.numel())
         return out, length, (t, ws)
 
     def _decompress_tensor(self, stream: torch.Tensor, dtype_code_tensor: torch.Tensor) -> torch.Tensor:
@@ -127,9 +124,7 @@ class ZPlaneCompressor(PatchCompressor):
                            f"dtype code ({dtype}) / length ({stream.numel()})")
         out = torch.empty(n.value, dtype=dtype, device=stream.device)
         status = torch.zeros(1, dtype=torch.int32, device=stream.device)
-        with torch.cuda.device(stream.device):
-            _lib.check(self._lib.rlx_zplane_decompress(stream.data_ptr(), stream.numel(), out.data_ptr(), n.value, es.value,
-                                                       status.data_ptr(), _stream_ptr(stream.device)), "rlx_zplane_decompress")
+        _lib.launch("rlx_zplane_decompress", stream.device, stream, stream.numel(), out, n.value, es.value, status)
         self._pending_status.append(status)
         return out
 

@@ -24,7 +24,6 @@ import torch
 
 from ... import _lib
 from ..._lib import RlxError
-from ...ops import _stream_ptr
 
 _FLOAT_CODES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 _RAW_BY_SIZE = {1: _lib.DTYPE_RAW8, 2: _lib.DTYPE_RAW16, 4: _lib.DTYPE_RAW32, 8: _lib.DTYPE_RAW64}
@@ -202,12 +201,9 @@ class PatchBuilder:
             n = value2d.numel()
             if n == 0:
                 continue
-            nbytes = lib.rlx_patch_workspace_bytes(n)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # one per tensor: all scans run before the first readback
+            ws = _lib.workspace(dev, lib.rlx_patch_workspace_bytes(n))  # one per tensor: all scans run before the first readback
             nnz = torch.zeros(1, dtype=torch.int64, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rlx_patch_scan(value2d.data_ptr(), vcode, snap.data_ptr(), scode, n, ws.data_ptr(), nbytes,
-                                              nnz.data_ptr(), _stream_ptr(dev)), "rlx_patch_scan")
+            _lib.launch("rlx_patch_scan", dev, value2d, vcode, snap, scode, n, ws, ws.numel(), nnz)
             staged.append((self.param_names_need_sync_ordinals[name], snap, value2d, vcode, scode, nnz, ws))
         if dev is None:
             raise RuntimeError("Snapshot contains no tensors")
@@ -220,11 +216,8 @@ class PatchBuilder:
             rows = torch.empty(nnz, dtype=torch.int64, device=dev)
             cols = torch.empty(nnz, dtype=torch.int64, device=dev)
             vals = torch.empty(nnz, dtype=snap.dtype, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rlx_patch_emit(value2d.data_ptr(), vcode, snap.data_ptr(), scode, value2d.numel(),
-                                              snap.shape[1], int(self.delta_encoding), ws.data_ptr(), nnz, rows.data_ptr(),
-                                              cols.data_ptr(), vals.data_ptr(), maxima.data_ptr(), _stream_ptr(dev)),
-                           "rlx_patch_emit")
+            _lib.launch("rlx_patch_emit", dev, value2d, vcode, snap, scode, value2d.numel(), snap.shape[1], int(self.delta_encoding),
+                        ws, nnz, rows, cols, vals, maxima)
             ords.append(ordinal), nnzs.append(nnz), rows_l.append(rows), cols_l.append(cols)
             vals_l.append(vals.view(torch.uint8))
         tdev = self.transport_device or dev
@@ -313,12 +306,9 @@ class CPUSnapshotPatchBuilder(PatchBuilder):
             n = value2d.numel()
             if n == 0:
                 continue
-            nbytes = lib.rlx_patch_workspace_bytes(n)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(dev, lib.rlx_patch_workspace_bytes(n))
             nnz = torch.zeros(1, dtype=torch.int64, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rlx_patch_scan(value2d.data_ptr(), vcode, snap.data_ptr(), scode, n, ws.data_ptr(), nbytes,
-                                              nnz.data_ptr(), _stream_ptr(dev)), "rlx_patch_scan")
+            _lib.launch("rlx_patch_scan", dev, value2d, vcode, snap, scode, n, ws, ws.numel(), nnz)
             staged_l.append((self.param_names_need_sync_ordinals[name], snap, value2d, vcode, scode, nnz, ws, host))
         if dev is None:
             raise RuntimeError("Snapshot contains no tensors")
@@ -332,11 +322,8 @@ class CPUSnapshotPatchBuilder(PatchBuilder):
             rows = torch.empty(nnz, dtype=torch.int64, device=dev)
             cols = torch.empty(nnz, dtype=torch.int64, device=dev)
             vals = torch.empty(nnz, dtype=snap.dtype, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rlx_patch_emit(value2d.data_ptr(), vcode, snap.data_ptr(), scode, value2d.numel(),
-                                              snap.shape[1], int(self.delta_encoding), ws.data_ptr(), nnz, rows.data_ptr(),
-                                              cols.data_ptr(), vals.data_ptr(), maxima.data_ptr(), _stream_ptr(dev)),
-                           "rlx_patch_emit")
+            _lib.launch("rlx_patch_emit", dev, value2d, vcode, snap, scode, value2d.numel(), snap.shape[1], int(self.delta_encoding),
+                        ws, nnz, rows, cols, vals, maxima)
             # the emit launch brought the staged copy up to date: it IS the new snapshot -> one sequential write-back
             cs.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(cs):
@@ -536,12 +523,8 @@ class PatchWeightSyncer:
             es = target.element_size()
             vals = payload.values[voff:voff + nnz * es].to(dev)
             off, voff = off + nnz, voff + nnz * es
-            ws_bytes = lib.rlx_patch_apply_workspace_bytes(nnz)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rlx_patch_apply(target.data_ptr(), _dtype_code(target.dtype), target.shape[0], target.shape[1],
-                                               rows.data_ptr(), _INDEX_CODES[rows.dtype], cols.data_ptr(),
-                                               _INDEX_CODES[cols.dtype], int(self.delta_encoding), vals.data_ptr(), nnz,
-                                               ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_patch_apply")
+            ws = _lib.workspace(dev, lib.rlx_patch_apply_workspace_bytes(nnz))
+            _lib.launch("rlx_patch_apply", dev, target, _dtype_code(target.dtype), target.shape[0], target.shape[1], rows,
+                        _INDEX_CODES[rows.dtype], cols, _INDEX_CODES[cols.dtype], int(self.delta_encoding), vals, nnz, ws, ws.numel())
         weights_changed(model_or_state_dict)
         return int(payload.version.item())

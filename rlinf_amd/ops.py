@@ -5,21 +5,16 @@ otherwise -- there is no eager/CPU path.
 
 from __future__ import annotations
 
-from ctypes import byref
-from typing import Optional
-
 import ctypes
 import os
+from ctypes import byref
+from typing import Optional
 
 import torch
 
 from . import _lib
 from ._lib import (AdamwGroup, AdamwParams, GaeParams, GatherField, MlpLayout, PpoLossParams, PpoStepArgs, RlxError,
                    RolloutStep)
-
-
-def _stream_ptr(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _dev(*tensors) -> torch.device:
@@ -36,10 +31,6 @@ def _dev(*tensors) -> torch.device:
     if dev is None:
         raise RlxError("no tensor argument")
     return dev
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _as_u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -68,7 +59,6 @@ def _nbc(t: torch.Tensor, name: str):
 
 def done_prefix_mask(dones: torch.Tensor):
     """dones bool [n+1, B, C] -> (loss_mask bool [n, B, C], mask_sum int64 [B]).  a9."""
-    lib = _lib.load()
     dev = _dev(dones)
     n1, B, C = _nbc(dones, "dones")
     if n1 < 1:
@@ -76,9 +66,7 @@ def done_prefix_mask(dones: torch.Tensor):
     d8 = _as_u8(dones)
     mask = torch.empty((n1 - 1, B, C), dtype=torch.bool, device=dev)
     cnt = torch.empty((B,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_done_prefix_mask(d8.data_ptr(), mask.data_ptr(), cnt.data_ptr(), n1 - 1, B, C,
-                                            _stream_ptr(dev)), "rlx_done_prefix_mask")
+    _lib.launch("rlx_done_prefix_mask", dev, d8, mask, cnt, n1 - 1, B, C)
     return mask, cnt
 
 
@@ -109,13 +97,10 @@ def gae_scan(rewards: torch.Tensor, values: Optional[torch.Tensor], dones: torch
     else:
         adv = torch.empty_like(r)
         ret = torch.empty_like(r)
-    ws_bytes = max(8, lib.rlx_gae_workspace_bytes(n, B, C))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(dev, max(8, lib.rlx_gae_workspace_bytes(n, B, C)))
     p = GaeParams(float(gamma), float(float(gamma) * float(gae_lambda)), int(bool(normalize_advantages)),
                   int(bool(normalize_returns)), float(norm_eps), int(variant))
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_gae_scan(r.data_ptr(), _ptr(v), d8.data_ptr(), _ptr(m8), adv.data_ptr(), ret.data_ptr(),
-                                    ws.data_ptr(), ws_bytes, n, B, C, byref(p), _stream_ptr(dev)), "rlx_gae_scan")
+    _lib.launch("rlx_gae_scan", dev, r, v, d8, m8, adv, ret, ws, ws.numel(), n, B, C, p)
     return adv, ret
 
 
@@ -128,11 +113,8 @@ def masked_standardize_(x: torch.Tensor, mask: Optional[torch.Tensor] = None, ep
     m8 = _as_u8(mask)
     if m8 is not None and m8.numel() != x.numel():
         raise RlxError("mask must have as many elements as x")
-    ws_bytes = lib.rlx_standardize_workspace_bytes(x.numel())
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_masked_standardize(x.data_ptr(), _ptr(m8), x.numel(), float(eps), ws.data_ptr(), ws_bytes,
-                                              _stream_ptr(dev)), "rlx_masked_standardize")
+    ws = _lib.workspace(dev, lib.rlx_standardize_workspace_bytes(x.numel()))
+    _lib.launch("rlx_masked_standardize", dev, x, m8, x.numel(), float(eps), ws, ws.numel())
     return x
 
 
@@ -148,11 +130,8 @@ def masked_stats(x: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Opti
         raise AssertionError((tuple(mask.shape), tuple(x.shape)))
     if out is None:
         out = torch.zeros(3, dtype=torch.float64, device=dev)
-    ws_bytes = lib.rlx_masked_stats_workspace_bytes(xf.numel())
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_masked_stats(xf.data_ptr(), _ptr(m8), xf.numel(), out.data_ptr(), int(bool(accumulate)),
-                                        ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_masked_stats")
+    ws = _lib.workspace(dev, lib.rlx_masked_stats_workspace_bytes(xf.numel()))
+    _lib.launch("rlx_masked_stats", dev, xf, m8, xf.numel(), out, int(bool(accumulate)), ws, ws.numel())
     return out
 
 
@@ -164,9 +143,8 @@ def normalize_from_stats(x: torch.Tensor, stats: torch.Tensor, out: Optional[tor
         raise RlxError("stats must be float64[3]")
     if out is None:
         out = torch.empty_like(xf)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_normalize_from_stats(xf.data_ptr(), stats.contiguous().data_ptr(), out.data_ptr(),
-                                                        xf.numel(), _stream_ptr(dev)), "rlx_normalize_from_stats")
+    st = stats.contiguous()
+    _lib.launch("rlx_normalize_from_stats", dev, xf, st, out, xf.numel())
     return out.view(x.shape)
 
 
@@ -183,16 +161,14 @@ def masked_normalize(x: torch.Tensor, mask: Optional[torch.Tensor], stats: torch
         raise RlxError("stats must be float64[3]")
     if out is None:
         out = torch.empty_like(xf)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_masked_normalize(xf.data_ptr(), _ptr(m8), stats.contiguous().data_ptr(), float(eps),
-                                                    out.data_ptr(), xf.numel(), _stream_ptr(dev)), "rlx_masked_normalize")
+    st = stats.contiguous()
+    _lib.launch("rlx_masked_normalize", dev, xf, m8, st, float(eps), out, xf.numel())
     return out.view(x.shape)
 
 
 def grpo_group_adv(rewards: torch.Tensor, dones: torch.Tensor, loss_mask: torch.Tensor, group_size: int,
                    eps: float = 1e-6):
     """rewards [n,B,C], dones [n+1,B,C], loss_mask [n,B,C] -> (advantages [n,B,C], scores [B]).  a13."""
-    lib = _lib.load()
     dev = _dev(rewards, dones, loss_mask)
     n, B, C = _nbc(rewards, "rewards")
     r = _as_f32(rewards, "rewards")
@@ -204,15 +180,12 @@ def grpo_group_adv(rewards: torch.Tensor, dones: torch.Tensor, loss_mask: torch.
         raise RlxError(f"batch {B} not divisible by group_size {group_size}")
     adv = torch.empty_like(r)
     scores = torch.empty((B,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_grpo_group_adv(r.data_ptr(), d8.data_ptr(), m8.data_ptr(), scores.data_ptr(), adv.data_ptr(),
-                                          n, B, C, int(group_size), float(eps), _stream_ptr(dev)), "rlx_grpo_group_adv")
+    _lib.launch("rlx_grpo_group_adv", dev, r, d8, m8, scores, adv, n, B, C, int(group_size), float(eps))
     return adv, scores
 
 
 def grpo_from_scores(scores: torch.Tensor, loss_mask: torch.Tensor, group_size: int, eps: float = 1e-6) -> torch.Tensor:
     """scores [B] f32, loss_mask [n,B,C] -> advantages [n,B,C] (advantages.py:107-121)."""
-    lib = _lib.load()
     dev = _dev(scores, loss_mask)
     n, B, C = _nbc(loss_mask, "loss_mask")
     sc = _as_f32(scores.reshape(-1), "scores")
@@ -220,9 +193,7 @@ def grpo_from_scores(scores: torch.Tensor, loss_mask: torch.Tensor, group_size: 
         raise RlxError(f"scores must have {B} elements and batch must divide by group_size={group_size}")
     m8 = _as_u8(loss_mask)
     adv = torch.empty((n, B, C), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_grpo_from_scores(sc.data_ptr(), m8.data_ptr(), adv.data_ptr(), n, B, C, int(group_size),
-                                            float(eps), _stream_ptr(dev)), "rlx_grpo_from_scores")
+    _lib.launch("rlx_grpo_from_scores", dev, sc, m8, adv, n, B, C, int(group_size), float(eps))
     return adv
 
 
@@ -236,17 +207,11 @@ def gaussian_entropy_bonus_(params: torch.Tensor, layout: MlpLayout, grads_slab0
     off, A = int(layout.off_logstd), int(layout.act_dim)
     logstd = params[off:off + A]
     g = grads_slab0[off:off + A]
+    argv = (logstd, A, g, out_row, float(entropy_bonus), float(grad_scale), int(bool(has_mask)), float(elem_scale))
     if actor_scale is not None:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().rlx_gaussian_entropy_bonus_deferred(
-                logstd.data_ptr(), A, g.data_ptr(), out_row.data_ptr(), float(entropy_bonus), float(grad_scale), int(bool(has_mask)),
-                float(elem_scale), actor_scale.data_ptr(), _stream_ptr(dev)), "rlx_gaussian_entropy_bonus_deferred")
-        return
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_gaussian_entropy_bonus(logstd.data_ptr(), A, g.data_ptr(), out_row.data_ptr(),
-                                                          float(entropy_bonus), float(grad_scale), int(bool(has_mask)),
-                                                          float(elem_scale), _stream_ptr(dev)),
-                   "rlx_gaussian_entropy_bonus")
+        _lib.launch("rlx_gaussian_entropy_bonus_deferred", dev, *argv, actor_scale)
+    else:
+        _lib.launch("rlx_gaussian_entropy_bonus", dev, *argv)
 
 
 def rollout_metrics(arrays: list, loss_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -263,10 +228,8 @@ def rollout_metrics(arrays: list, loss_mask: Optional[torch.Tensor] = None, out:
     sizes = (ctypes.c_int64 * k)(*[x.numel() for x in xs])
     out = torch.empty((k, 4), dtype=torch.float64, device=dev) if out is None else out
     wsb = lib.rlx_rollout_metrics_workspace_bytes()
-    ws = workspace if workspace is not None and workspace.numel() >= wsb else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_rollout_metrics(ptrs, sizes, k, _ptr(m8), 0 if m8 is None else m8.numel(), out.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), _stream_ptr(dev)), "rlx_rollout_metrics")
+    ws = workspace if workspace is not None and workspace.numel() >= wsb else _lib.workspace(dev, wsb)
+    _lib.launch("rlx_rollout_metrics", dev, ptrs, sizes, k, m8, 0 if m8 is None else m8.numel(), out, ws, ws.numel())
     return out
 
 
@@ -283,16 +246,12 @@ def reward_filter_mask(rewards: torch.Tensor, loss_mask: Optional[torch.Tensor],
     if group_size < 1 or B % group_size != 0:
         raise AssertionError(f"batch {B} not divisible by group_size {group_size}")
     out = torch.empty((n, B, C if m is not None else 1), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_reward_filter_mask(r.data_ptr(), _ptr(m), out.data_ptr(), n, B, C, int(group_size),
-                                                      float(lower), float(upper), _stream_ptr(dev)),
-                   "rlx_reward_filter_mask")
+    _lib.launch("rlx_reward_filter_mask", dev, r, m, out, n, B, C, int(group_size), float(lower), float(upper))
     return out.view(torch.bool)
 
 
 def episode_scores(rewards: torch.Tensor, dones: torch.Tensor) -> torch.Tensor:
     """rewards [n,B,C], dones [n+1,B,C] -> per-env first-episode return [B] (utils.py:134-152)."""
-    lib = _lib.load()
     dev = _dev(rewards, dones)
     n, B, C = _nbc(rewards, "rewards")
     r = _as_f32(rewards, "rewards")
@@ -300,9 +259,7 @@ def episode_scores(rewards: torch.Tensor, dones: torch.Tensor) -> torch.Tensor:
     if tuple(d8.shape) != (n + 1, B, C):
         raise RlxError("dones must be [n+1,B,C]")
     scores = torch.empty((B,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_episode_scores(r.data_ptr(), d8.data_ptr(), scores.data_ptr(), n, B, C, _stream_ptr(dev)),
-                   "rlx_episode_scores")
+    _lib.launch("rlx_episode_scores", dev, r, d8, scores, n, B, C)
     return scores
 
 
@@ -311,7 +268,6 @@ def grpo_video_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: i
     moments for mode "frame", per prompt for "video".  a13b."""
     if mode not in _lib.GRPO_VIDEO_MODES:
         raise ValueError(f"Unsupported grpo_video advantage_mode: {mode}")
-    lib = _lib.load()
     dev = _dev(rewards, loss_mask)
     n, B, C = _nbc(rewards, "rewards")
     r = _as_f32(rewards, "rewards")
@@ -321,9 +277,7 @@ def grpo_video_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: i
     if group_size < 1 or B % group_size != 0:
         raise RlxError(f"batch {B} not divisible by group_size {group_size}")
     adv = torch.empty_like(r)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_grpo_video_adv(r.data_ptr(), m8.data_ptr(), adv.data_ptr(), n, B, C, int(group_size),
-                                          _lib.GRPO_VIDEO_MODES[mode], float(eps), _stream_ptr(dev)), "rlx_grpo_video_adv")
+    _lib.launch("rlx_grpo_video_adv", dev, r, m8, adv, n, B, C, int(group_size), _lib.GRPO_VIDEO_MODES[mode], float(eps))
     return adv
 
 
@@ -343,11 +297,9 @@ def raw_adv(scores: torch.Tensor, loss_mask: torch.Tensor, normalize: bool = Fal
         raise RlxError(f"scores must have {batch} elements, got {sc.numel()}")
     m8 = _as_u8(loss_mask)
     adv = torch.empty(tuple(loss_mask.shape), dtype=torch.float32, device=dev)
-    ws_bytes = lib.rlx_raw_adv_workspace_bytes(outer, batch, inner) if normalize else 0
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if normalize else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_raw_adv(sc.data_ptr(), m8.data_ptr(), adv.data_ptr(), outer, batch, inner, int(bool(normalize)),
-                                   float(eps), _ptr(ws), ws_bytes, _stream_ptr(dev)), "rlx_raw_adv")
+    ws = _lib.workspace(dev, lib.rlx_raw_adv_workspace_bytes(outer, batch, inner)) if normalize else None
+    _lib.launch("rlx_raw_adv", dev, sc, m8, adv, outer, batch, inner, int(bool(normalize)), float(eps), ws,
+                ws.numel() if normalize else 0)
     return adv
 
 
@@ -389,15 +341,12 @@ def _loss_geometry(logprobs: torch.Tensor, logprob_type: str, action_dim: int, r
 
 def _loss_forward(ctx, logprobs, values, params: PpoLossParams, n_adv: int, workspace_bytes, launch):
     """The forward both loss nodes share: per-element gradient factors, the metric row and the workspace are allocated here,
-    ``launch(lp, g_lp, g_v, out, ws, ws_bytes)`` issues the node's own forward, ``ctx`` keeps what rlx_ppo_loss_bwd needs."""
+    ``launch(lp, g_lp, g_v, out, ws)`` issues the node's own forward, ``ctx`` keeps what rlx_ppo_loss_bwd needs."""
     dev = logprobs.device
     g_lp = torch.empty((n_adv * params.sub_per_adv,), dtype=torch.float32, device=dev)
     g_v = torch.empty((n_adv,), dtype=torch.float32, device=dev) if params.has_critic else None
     out = torch.empty((_lib.PPO_OUT_FLOATS,), dtype=torch.float32, device=dev)
-    ws_bytes = workspace_bytes(n_adv)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        launch(logprobs.contiguous(), g_lp, g_v, out, ws, ws_bytes)
+    launch(logprobs.contiguous(), g_lp, g_v, out, _lib.workspace(dev, workspace_bytes(n_adv)))
     ctx.save_for_backward(g_lp, g_v if g_v is not None else out, out)
     ctx.has_critic = bool(params.has_critic)
     ctx.geom = (n_adv, params.raw_per_adv, params.sub_per_adv)
@@ -413,27 +362,21 @@ class _PpoLossFn(torch.autograd.Function):
                 params: PpoLossParams, n_adv: int):
         lib = _lib.load()
 
-        def launch(lp, g_lp, g_v, out, ws, ws_bytes):
-            _lib.check(lib.rlx_ppo_loss_fwd(lp.data_ptr(), old_logprobs.data_ptr(), advantages.data_ptr(), _ptr(values),
-                                            _ptr(prev_values), _ptr(returns), _ptr(loss_mask), _ptr(loss_mask_sum), n_adv,
-                                            byref(params), g_lp.data_ptr(), _ptr(g_v), out.data_ptr(), ws.data_ptr(),
-                                            ws_bytes, _stream_ptr(lp.device)), "rlx_ppo_loss_fwd")
+        def launch(lp, g_lp, g_v, out, ws):
+            _lib.launch("rlx_ppo_loss_fwd", lp.device, lp, old_logprobs, advantages, values, prev_values, returns, loss_mask,
+                        loss_mask_sum, n_adv, params, g_lp, g_v, out, ws, ws.numel())
 
         return _loss_forward(ctx, logprobs, values, params, n_adv, lib.rlx_ppo_loss_workspace_bytes, launch)
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_out):
-        lib = _lib.load()
         g_lp, g_v, out = ctx.saved_tensors
         n_adv, raw, sub = ctx.geom
         dev = g_lp.device
         go = grad_loss.to(dtype=torch.float32).contiguous()
         d_lp = torch.empty((n_adv * raw,), dtype=torch.float32, device=dev)
         d_v = torch.empty((n_adv,), dtype=torch.float32, device=dev) if ctx.has_critic else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.rlx_ppo_loss_bwd(g_lp.data_ptr(), g_v.data_ptr() if ctx.has_critic else None, out.data_ptr(),
-                                            go.data_ptr(), d_lp.data_ptr(), _ptr(d_v), n_adv, raw, sub,
-                                            _stream_ptr(dev)), "rlx_ppo_loss_bwd")
+        _lib.launch("rlx_ppo_loss_bwd", dev, g_lp, g_v if ctx.has_critic else None, out, go, d_lp, d_v, n_adv, raw, sub)
         return (d_lp.view(ctx.lp_shape), None if d_v is None else d_v.view(ctx.v_shape), None, None, None, None, None,
                 None, None, None)
 
@@ -529,12 +472,9 @@ class _DecoupledLossFn(torch.autograd.Function):
                 proximal_logprobs, versions, dp, n_adv: int):
         lib = _lib.load()
 
-        def launch(lp, g_lp, g_v, out, ws, ws_bytes):
-            _lib.check(lib.rlx_decoupled_loss_fwd(
-                lp.data_ptr(), old_logprobs.data_ptr(), _ptr(proximal_logprobs), _ptr(versions), advantages.data_ptr(),
-                _ptr(values), _ptr(prev_values), _ptr(returns), _ptr(loss_mask), _ptr(loss_mask_sum), n_adv, byref(dp),
-                g_lp.data_ptr(), _ptr(g_v), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(lp.device)),
-                "rlx_decoupled_loss_fwd")
+        def launch(lp, g_lp, g_v, out, ws):
+            _lib.launch("rlx_decoupled_loss_fwd", lp.device, lp, old_logprobs, proximal_logprobs, versions, advantages, values,
+                        prev_values, returns, loss_mask, loss_mask_sum, n_adv, dp, g_lp, g_v, out, ws, ws.numel())
 
         return _loss_forward(ctx, logprobs, values, dp.ppo, n_adv, lib.rlx_decoupled_loss_workspace_bytes, launch)
 
@@ -566,22 +506,13 @@ def make_ppo_params(*, logprob_type="action_level", action_dim=8, chunks=1, clip
 def ppo_loss_fwd_raw(params: PpoLossParams, n_adv: int, logprobs, old_logprobs, advantages, values, prev_values, returns,
                      loss_mask, loss_mask_sum, g_logp, g_value, out, workspace):
     """Allocation-free launcher (all tensors caller-owned) used by the learner's fused/graph-captured step."""
-    lib = _lib.load()
-    dev = logprobs.device
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_ppo_loss_fwd(logprobs.data_ptr(), old_logprobs.data_ptr(), advantages.data_ptr(), _ptr(values),
-                                        _ptr(prev_values), _ptr(returns), _ptr(loss_mask), _ptr(loss_mask_sum), n_adv,
-                                        byref(params), g_logp.data_ptr(), _ptr(g_value), out.data_ptr(),
-                                        workspace.data_ptr(), workspace.numel(), _stream_ptr(dev)), "rlx_ppo_loss_fwd")
+    _lib.launch("rlx_ppo_loss_fwd", logprobs.device, logprobs, old_logprobs, advantages, values, prev_values, returns, loss_mask,
+                loss_mask_sum, n_adv, params, g_logp, g_value, out, workspace, workspace.numel())
 
 
 def ppo_loss_bwd_raw(params: PpoLossParams, n_adv: int, g_logp, g_value, out, grad_out, d_logprobs, d_values):
-    lib = _lib.load()
-    dev = g_logp.device
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_ppo_loss_bwd(g_logp.data_ptr(), _ptr(g_value), out.data_ptr(), _ptr(grad_out),
-                                        d_logprobs.data_ptr(), _ptr(d_values), n_adv, params.raw_per_adv, params.sub_per_adv,
-                                        _stream_ptr(dev)), "rlx_ppo_loss_bwd")
+    _lib.launch("rlx_ppo_loss_bwd", g_logp.device, g_logp, g_value, out, grad_out, d_logprobs, d_values, n_adv, params.raw_per_adv,
+                params.sub_per_adv)
 
 
 # --------------------------------------------------------------------------------------------
@@ -605,7 +536,6 @@ def opd_advantages(teacher_logprobs: torch.Tensor, prev_logprobs: torch.Tensor, 
                    rows: Optional[int] = None) -> torch.Tensor:
     """(teacher.float() - prev.float()) reshaped to [..., C, A], first ``rows`` entries of dim 0 (all when None): ONE launch of
     rlx_opd_advantages, f32 out.  The caller has checked shapes (algorithms/advantages.py holds the reference's asserts)."""
-    lib = _lib.load()
     dev = _dev(teacher_logprobs, prev_logprobs)
     t = _opd_rows(teacher_logprobs, int(num_action_chunks))
     p = _opd_rows(prev_logprobs, int(num_action_chunks))
@@ -616,10 +546,8 @@ def opd_advantages(teacher_logprobs: torch.Tensor, prev_logprobs: torch.Tensor, 
         raise RlxError(f"rows={n_rows} outside [0, {t.shape[0]}]")
     out = torch.empty((n_rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
     inner = out[0].numel() if n_rows > 0 else 0
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_opd_advantages(t.data_ptr(), _OPD_DTYPES[t.dtype], t.stride(0) if t.dim() else 1, p.data_ptr(),
-                                          _OPD_DTYPES[p.dtype], p.stride(0) if p.dim() else 1, n_rows, inner, out.data_ptr(),
-                                          _stream_ptr(dev)), "rlx_opd_advantages")
+    _lib.launch("rlx_opd_advantages", dev, t, _OPD_DTYPES[t.dtype], t.stride(0) if t.dim() else 1, p, _OPD_DTYPES[p.dtype],
+                p.stride(0) if p.dim() else 1, n_rows, inner, out)
     return out
 
 
@@ -645,12 +573,9 @@ class _OpdLossFn(torch.autograd.Function):
         n = lp.numel()
         i64 = int(loss_mask_sum is not None and loss_mask_sum.dtype == torch.int64)
         out = torch.empty((_lib.OPD_OUT_FLOATS,), dtype=torch.float32, device=dev)
-        ws_bytes = lib.rlx_opd_loss_workspace_bytes(n)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.rlx_opd_loss_fwd(lp.data_ptr(), advantages.data_ptr(), loss_mask.data_ptr(), mask_div,
-                                            _ptr(loss_mask_sum), msum_div, i64, n, max_episode_steps, out.data_ptr(),
-                                            ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_opd_loss_fwd")
+        ws = _lib.workspace(dev, lib.rlx_opd_loss_workspace_bytes(n))
+        _lib.launch("rlx_opd_loss_fwd", dev, lp, advantages, loss_mask, mask_div, loss_mask_sum, msum_div, i64, n, max_episode_steps,
+                    out, ws, ws.numel())
         ctx.save_for_backward(advantages, loss_mask, loss_mask_sum if loss_mask_sum is not None else out, out)
         ctx.geom = (mask_div, msum_div, i64, n, max_episode_steps, loss_mask_sum is not None)
         ctx.lp_shape = logprobs.shape
@@ -659,16 +584,12 @@ class _OpdLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_out):
-        lib = _lib.load()
         adv, mask, msum, out = ctx.saved_tensors
         mask_div, msum_div, i64, n, mes, has_msum = ctx.geom
         dev = adv.device
         go = grad_loss.to(dtype=torch.float32).contiguous()
         d_lp = torch.empty((n,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.rlx_opd_loss_bwd(adv.data_ptr(), mask.data_ptr(), mask_div, msum.data_ptr() if has_msum else None,
-                                            msum_div, i64, n, mes, out.data_ptr(), go.data_ptr(), d_lp.data_ptr(),
-                                            _stream_ptr(dev)), "rlx_opd_loss_bwd")
+        _lib.launch("rlx_opd_loss_bwd", dev, adv, mask, mask_div, msum if has_msum else None, msum_div, i64, n, mes, out, go, d_lp)
         return d_lp.view(ctx.lp_shape), None, None, None, None, None, None
 
 
@@ -680,7 +601,7 @@ def opd_loss(logprobs: torch.Tensor, advantages: torch.Tensor, loss_mask: torch.
     per row (the reference's broadcast of a last dimension of 1).  ``max_episode_steps`` selects masked_mean_ratio with
     ratio = loss_mask_sum / max_episode_steps, else masked_mean.  Returns (loss 0-dim with grad, out f32[8] on device, see
     _lib.OPD_OUT_NAMES)."""
-    dev = _dev(logprobs, advantages, loss_mask, loss_mask_sum)
+    _dev(logprobs, advantages, loss_mask, loss_mask_sum)
     for name, t in (("logprobs", logprobs), ("advantages", advantages)):
         if t.dtype != torch.float32:
             raise RlxError(f"{name} must be float32 to keep numerical stability")
@@ -703,8 +624,7 @@ def opd_loss(logprobs: torch.Tensor, advantages: torch.Tensor, loss_mask: torch.
         msum = loss_mask_sum if loss_mask_sum.dtype in (torch.int64, torch.float32) else loss_mask_sum.float()
         msum = msum.contiguous()
         sdiv = _opd_div(msum, n, int(action_dim), "loss_mask_sum")
-    with torch.cuda.device(dev):
-        return _OpdLossFn.apply(logprobs, advantages.detach().contiguous(), m8, mdiv, msum, sdiv, mes)
+    return _OpdLossFn.apply(logprobs, advantages.detach().contiguous(), m8, mdiv, msum, sdiv, mes)
 
 
 # --------------------------------------------------------------------------------------------
@@ -712,7 +632,6 @@ def opd_loss(logprobs: torch.Tensor, advantages: torch.Tensor, loss_mask: torch.
 # --------------------------------------------------------------------------------------------
 def gather_rows(fields: list, index: torch.Tensor, outs: Optional[list] = None) -> list:
     """fields: list of [N, ...] contiguous HIP tensors; returns [t[index] for t in fields] (one launch per 16)."""
-    lib = _lib.load()
     if not fields:
         return []
     dev = _dev(index, *fields)
@@ -725,19 +644,18 @@ def gather_rows(fields: list, index: torch.Tensor, outs: Optional[list] = None) 
             raise RlxError("gather_rows needs contiguous fields")
     if outs is None:
         outs = [torch.empty((n, *t.shape[1:]), dtype=t.dtype, device=dev) for t in fields]
-    with torch.cuda.device(dev):
-        for lo in range(0, len(fields), _lib.GATHER_MAX_FIELDS):
-            chunk = list(zip(fields, outs))[lo:lo + _lib.GATHER_MAX_FIELDS]
-            arr = (GatherField * len(chunk))()
-            k = 0
-            for src, dst in chunk:
-                row_bytes = src.element_size() * (src.numel() // max(src.shape[0], 1))
-                if row_bytes == 0:
-                    continue
-                arr[k].src, arr[k].dst, arr[k].row_bytes = src.data_ptr(), dst.data_ptr(), row_bytes
-                k += 1
-            if k and n:
-                _lib.check(lib.rlx_gather_rows(arr, k, idx.data_ptr(), n, _stream_ptr(dev)), "rlx_gather_rows")
+    for lo in range(0, len(fields), _lib.GATHER_MAX_FIELDS):
+        chunk = list(zip(fields, outs))[lo:lo + _lib.GATHER_MAX_FIELDS]
+        arr = (GatherField * len(chunk))()
+        k = 0
+        for src, dst in chunk:
+            row_bytes = src.element_size() * (src.numel() // max(src.shape[0], 1))
+            if row_bytes == 0:
+                continue
+            arr[k].src, arr[k].dst, arr[k].row_bytes = src.data_ptr(), dst.data_ptr(), row_bytes
+            k += 1
+        if k and n:
+            _lib.launch("rlx_gather_rows", dev, arr, k, idx, n)
     return outs
 
 
@@ -756,14 +674,11 @@ def version_stats(versions: torch.Tensor, base: int, n_bins: int = _lib.VERSION_
                   ) -> _lib.VersionStats:
     """One pass over a trajectory's contiguous f32 ``versions`` -> the host copy of rlx_version_stats_out (min, n, the exact sum
     of the rounded versions, count[k] of round(v) - base == k, below / above the bin range).  One read-back."""
-    lib = _lib.load()
     dev = _dev(versions)
     if versions.dtype != torch.float32 or not versions.is_contiguous():
         raise RlxError("version_stats needs a contiguous float32 tensor")
     out, ws = workspace if workspace is not None else version_stats_workspace(dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_version_stats(versions.data_ptr(), versions.numel(), int(base), int(n_bins), out.data_ptr(), ws.data_ptr(),
-                                         ws.numel() * 8, _stream_ptr(dev)), "rlx_version_stats")
+    _lib.launch("rlx_version_stats", dev, versions, versions.numel(), int(base), int(n_bins), out, ws, ws.numel() * 8)
     host = out.cpu()  # the one read-back per added trajectory
     return _lib.VersionStats.from_buffer_copy(host.numpy().tobytes())
 
@@ -772,7 +687,6 @@ def gather_rows_segmented(slot_fields: list, index: Optional[torch.Tensor], outs
     """``slot_fields``: per field the list of its S per-slot tensors, each a contiguous ``[t_rows, B_s, ...]`` block (B_s the same
     for every field of a slot; t_rows may differ between fields).  -> per field ``cat(slots, dim=1).flatten(0, 1)[index]``, or with
     ``index=None`` the concatenation itself ``[t_rows, sum B, ...]`` -- one launch per 16 fields, no concatenated intermediate."""
-    lib = _lib.load()
     if not slot_fields:
         return []
     S = len(slot_fields[0])
@@ -798,22 +712,20 @@ def gather_rows_segmented(slot_fields: list, index: Optional[torch.Tensor], outs
         outs = [torch.empty((n, *f[0].shape[2:]) if index is not None else (f[0].shape[0], sum_b, *f[0].shape[2:]),
                             dtype=f[0].dtype, device=dev) for f in slot_fields]
     env_table = (ctypes.c_int64 * S)(*envs)
-    with torch.cuda.device(dev):
-        for lo in range(0, len(slot_fields), _lib.GATHER_MAX_FIELDS):
-            chunk = list(zip(slot_fields, outs))[lo:lo + _lib.GATHER_MAX_FIELDS]
-            arr, tables, k = (_lib.SegField * len(chunk))(), [], 0
-            for f, dst in chunk:
-                row_bytes = f[0].element_size() * (f[0][0, 0].numel() if f[0].dim() > 2 else 1)
-                if row_bytes == 0 or f[0].shape[0] == 0:
-                    continue
-                if not dst.is_contiguous():
-                    raise RlxError("gather_rows_segmented needs contiguous destinations")
-                tables.append((ctypes.c_void_p * S)(*[t.data_ptr() for t in f]))
-                arr[k].srcs, arr[k].dst, arr[k].row_bytes, arr[k].t_rows = tables[-1], dst.data_ptr(), row_bytes, f[0].shape[0]
-                k += 1
-            if k and (index is None or n):
-                _lib.check(lib.rlx_gather_rows_segmented(arr, k, S, env_table, _ptr(index), n, _stream_ptr(dev)),
-                           "rlx_gather_rows_segmented")
+    for lo in range(0, len(slot_fields), _lib.GATHER_MAX_FIELDS):
+        chunk = list(zip(slot_fields, outs))[lo:lo + _lib.GATHER_MAX_FIELDS]
+        arr, tables, k = (_lib.SegField * len(chunk))(), [], 0
+        for f, dst in chunk:
+            row_bytes = f[0].element_size() * (f[0][0, 0].numel() if f[0].dim() > 2 else 1)
+            if row_bytes == 0 or f[0].shape[0] == 0:
+                continue
+            if not dst.is_contiguous():
+                raise RlxError("gather_rows_segmented needs contiguous destinations")
+            tables.append((ctypes.c_void_p * S)(*[t.data_ptr() for t in f]))
+            arr[k].srcs, arr[k].dst, arr[k].row_bytes, arr[k].t_rows = tables[-1], dst.data_ptr(), row_bytes, f[0].shape[0]
+            k += 1
+        if k and (index is None or n):
+            _lib.launch("rlx_gather_rows_segmented", dev, arr, k, S, env_table, index, n)
     return outs
 
 
@@ -918,19 +830,15 @@ def clip_adamw_step_(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.T
     if stats is None:
         stats = torch.empty((2,), dtype=torch.float32, device=dev)
     ws_bytes = lib.rlx_adamw_workspace_bytes(n)
-    ws = workspace if workspace is not None and workspace.numel() >= ws_bytes else torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ws = workspace if workspace is not None and workspace.numel() >= ws_bytes else _lib.workspace(dev, ws_bytes)
     if step_state is not None and (step_state.dtype != torch.int32 or step_state.numel() < 2):
         raise RlxError("step_state must be int32[2]")
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_clip_adamw_step(params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-                                           byref(p), stats.data_ptr(), _ptr(step_state), ws.data_ptr(), ws.numel(),
-                                           _stream_ptr(dev)), "rlx_clip_adamw_step")
+    _lib.launch("rlx_clip_adamw_step", dev, params, grads, exp_avg, exp_avg_sq, n, p, stats, step_state, ws, ws.numel())
     return stats
 
 
 def bootstrap_rewards_(rewards: torch.Tensor, flags: torch.Tensor, bootstrap_values: torch.Tensor, gamma: float):
     """rewards [B,C] f32 in place: r[:, -1] += gamma * V[:, 0] where flags[:, -1]  (env_worker.py:744-758)."""
-    lib = _lib.load()
     dev = _dev(rewards, flags, bootstrap_values)
     if rewards.dim() != 2 or not rewards.is_contiguous() or rewards.dtype != torch.float32:
         raise RlxError("rewards must be a contiguous float32 [B, C] tensor")
@@ -939,15 +847,12 @@ def bootstrap_rewards_(rewards: torch.Tensor, flags: torch.Tensor, bootstrap_val
     B, C = rewards.shape
     if tuple(f8.shape) != (B, C) or v.shape[0] != B:
         raise RlxError("flags must be [B,C] and bootstrap_values [B, >=1]")
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_bootstrap_rewards(rewards.data_ptr(), f8.data_ptr(), v.data_ptr(), B, C,
-                                             v.numel() // max(B, 1), float(gamma), _stream_ptr(dev)), "rlx_bootstrap_rewards")
+    _lib.launch("rlx_bootstrap_rewards", dev, rewards, f8, v, B, C, v.numel() // max(B, 1), float(gamma))
     return rewards
 
 
 def store_env_rows_(rewards, terminations, truncations, reward_row, done_row, termination_row, truncation_row):
     """One env step's [B, C] outputs -> buffer rows; dones = terminations | truncations.  One launch."""
-    lib = _lib.load()
     dev = _dev(rewards, terminations, truncations, reward_row, done_row, termination_row, truncation_row)
     r = _as_f32(rewards, "rewards")
     te, tr = _as_u8(terminations), _as_u8(truncations)
@@ -955,10 +860,7 @@ def store_env_rows_(rewards, terminations, truncations, reward_row, done_row, te
     for t in (te, tr, reward_row, done_row, termination_row, truncation_row):
         if t.numel() != n or not t.is_contiguous():
             raise RlxError("store_env_rows_: all tensors must be contiguous with rewards' number of elements")
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_store_env_rows(r.data_ptr(), te.data_ptr(), tr.data_ptr(), reward_row.data_ptr(),
-                                          done_row.data_ptr(), termination_row.data_ptr(), truncation_row.data_ptr(), n,
-                                          _stream_ptr(dev)), "rlx_store_env_rows")
+    _lib.launch("rlx_store_env_rows", dev, r, te, tr, reward_row, done_row, termination_row, truncation_row, n)
 
 
 # --------------------------------------------------------------------------------------------
@@ -970,8 +872,7 @@ def mlp_pack(params: torch.Tensor, layout: MlpLayout, packed: Optional[torch.Ten
     nbytes = lib.rlx_mlp_packed_bytes(byref(layout))
     if packed is None:
         packed = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_pack(params.data_ptr(), byref(layout), packed.data_ptr(), _stream_ptr(dev)), "rlx_mlp_pack")
+    _lib.launch("rlx_mlp_pack", dev, params, layout, packed)
     return packed
 
 
@@ -989,7 +890,6 @@ def _rollout_outputs(out: Optional[tuple], M: int, layout: MlpLayout, dev, who: 
 def mlp_rollout(params: torch.Tensor, packed: torch.Tensor, layout: MlpLayout, states: torch.Tensor,
                 eps: Optional[torch.Tensor], out: Optional[tuple] = None):
     """states [M,D], eps [M,act]|None -> (action [M,act], logprob [M,act], value [M,val])."""
-    lib = _lib.load()
     dev = _dev(params, packed, states, eps)
     st = _as_f32(states, "states")
     M = st.shape[0]
@@ -999,48 +899,38 @@ def mlp_rollout(params: torch.Tensor, packed: torch.Tensor, layout: MlpLayout, s
     if e is not None and tuple(e.shape) != (M, layout.act_dim):
         raise RlxError(f"eps must be [{M}, {layout.act_dim}]")
     action, logprob, value = _rollout_outputs(out, M, layout, dev, "mlp_rollout")
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_rollout(params.data_ptr(), packed.data_ptr(), byref(layout), st.data_ptr(), _ptr(e), M,
-                                       action.data_ptr(), logprob.data_ptr(), value.data_ptr(), _stream_ptr(dev)),
-                   "rlx_mlp_rollout")
+    _lib.launch("rlx_mlp_rollout", dev, params, packed, layout, st, e, M, action, logprob, value)
     return action, logprob, value
 
 
 def mlp_value(params, packed, layout: MlpLayout, states, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Value head only: states [M,D] -> value [M,val]."""
-    lib = _lib.load()
     dev = _dev(params, packed, states)
     st = _as_f32(states, "states")
     M = st.shape[0]
     value = out if out is not None else torch.empty((M, layout.val_dim), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_value(params.data_ptr(), packed.data_ptr(), byref(layout), st.data_ptr(), M, value.data_ptr(),
-                                     _stream_ptr(dev)), "rlx_mlp_value")
+    _lib.launch("rlx_mlp_value", dev, params, packed, layout, st, M, value)
     return value
 
 
 def sum_slabs(grads: torch.Tensor, out: Optional[torch.Tensor] = None, deferred: Optional[dict] = None) -> torch.Tensor:
     """[slabs, n] -> [n].  ``deferred`` (deferred_actor_scale): the slabs are micro-batch groups behind decoupled ppo_steps."""
-    lib = _lib.load()
     dev = _dev(grads)
     slabs, n = grads.shape
     if out is None:
         out = torch.empty((n,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if deferred is not None:
-            p = AdamwParams()
-            _set_deferred(p, deferred)
-            _lib.check(lib.rlx_sum_slabs_deferred(grads.data_ptr(), n, slabs, out.data_ptr(), byref(p), _stream_ptr(dev)),
-                       "rlx_sum_slabs_deferred")
-        else:
-            _lib.check(lib.rlx_sum_slabs(grads.data_ptr(), n, slabs, out.data_ptr(), _stream_ptr(dev)), "rlx_sum_slabs")
+    if deferred is not None:
+        p = AdamwParams()
+        _set_deferred(p, deferred)
+        _lib.launch("rlx_sum_slabs_deferred", dev, grads, n, slabs, out, p)
+    else:
+        _lib.launch("rlx_sum_slabs", dev, grads, n, slabs, out)
     return out
 
 
 def mlp_train_fwd(params, packed, layout: MlpLayout, states, action, acts: Optional[torch.Tensor] = None,
                   out: Optional[tuple] = None):
     """-> (logprob, entropy [M,act], value [M,val], mean [M,act], acts [2,3,M,256])."""
-    lib = _lib.load()
     dev = _dev(params, packed, states, action)
     st, ac = _as_f32(states, "states"), _as_f32(action, "action")
     M = st.shape[0]
@@ -1055,10 +945,7 @@ def mlp_train_fwd(params, packed, layout: MlpLayout, states, action, acts: Optio
         value = torch.empty((M, layout.val_dim), dtype=torch.float32, device=dev)
     if acts is None or acts.numel() != 6 * M * 256:
         acts = torch.empty((2, 3, M, 256), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_train_fwd(params.data_ptr(), packed.data_ptr(), byref(layout), st.data_ptr(), ac.data_ptr(), M,
-                                         logprob.data_ptr(), entropy.data_ptr(), value.data_ptr(), mean.data_ptr(),
-                                         acts.data_ptr(), _stream_ptr(dev)), "rlx_mlp_train_fwd")
+    _lib.launch("rlx_mlp_train_fwd", dev, params, packed, layout, st, ac, M, logprob, entropy, value, mean, acts)
     return logprob, entropy, value, mean, acts
 
 
@@ -1077,14 +964,11 @@ def mlp_train_bwd(params, packed, layout: MlpLayout, states, action, mean, acts,
         grads = torch.empty((slabs, layout.n_params), dtype=torch.float32, device=dev)
     ws_bytes = lib.rlx_mlp_bwd_workspace_bytes(byref(layout), M)
     if workspace is None or workspace.numel() < ws_bytes:
-        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        workspace = _lib.workspace(dev, ws_bytes)
     dl, dv = _as_f32(d_logprob, "d_logprob"), _as_f32(d_value, "d_value")
     de = _as_f32(d_entropy, "d_entropy")
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_train_bwd(params.data_ptr(), packed.data_ptr(), byref(layout), states.data_ptr(),
-                                         action.data_ptr(), mean.data_ptr(), acts.data_ptr(), dl.data_ptr(), _ptr(de),
-                                         dv.data_ptr(), M, grads.data_ptr(), slabs, workspace.data_ptr(),
-                                         workspace.numel(), _stream_ptr(dev)), "rlx_mlp_train_bwd")
+    _lib.launch("rlx_mlp_train_bwd", dev, params, packed, layout, states, action, mean, acts, dl, de, dv, M, grads, slabs, workspace,
+                workspace.numel())
     return grads
 
 
@@ -1099,9 +983,7 @@ def mlp_pack_tiles(params: torch.Tensor, layout: MlpLayout, tiles: Optional[torc
     n = lib.rlx_mlp_tiles_bytes_for(byref(layout), 1 if bf16 else 0) // (2 if bf16 else 4)  # the f32 image is opaque (include/rlx.h)
     if tiles is None or tiles.dtype != dt or tiles.numel() != n:
         tiles = torch.empty((n,), dtype=dt, device=dev)
-    fn = lib.rlx_mlp_pack_tiles_bf16 if bf16 else lib.rlx_mlp_pack_tiles
-    with torch.cuda.device(dev):
-        _lib.check(fn(params.data_ptr(), byref(layout), tiles.data_ptr(), _stream_ptr(dev)), "rlx_mlp_pack_tiles")
+    _lib.launch("rlx_mlp_pack_tiles_bf16" if bf16 else "rlx_mlp_pack_tiles", dev, params, layout, tiles)
     return tiles
 
 
@@ -1113,7 +995,6 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
     rewards[:, -1] += gamma * V(states)[:, 0] where flags[:, -1].  With ``env=(rewards, terminations, truncations)`` and
     ``rows=(done_row, termination_row, truncation_row)`` the job also stores the env step's outputs into the buffer rows
     (``rewards`` is then the destination row; the flag is done, or truncation with ``flag_is_truncation``)."""
-    lib = _lib.load()
     dev = _dev(params, states, eps, *[j["states"] for j in value_jobs])
     st = RolloutStep()
     st.params, st.tiles, st.layout = params.data_ptr(), tiles.data_ptr(), ctypes_pointer(layout)
@@ -1131,8 +1012,9 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
         if states_copy is not None and (states_copy.dtype != torch.float32 or not states_copy.is_contiguous()
                                         or states_copy.numel() != s_.numel()):
             raise RlxError("mlp_rollout_step: states_copy must be a contiguous float32 tensor shaped like states")
-        st.states, st.eps, st.m = s_.data_ptr(), _ptr(e), M
-        st.action, st.logprob, st.value, st.states_copy = action.data_ptr(), logprob.data_ptr(), value.data_ptr(), _ptr(states_copy)
+        st.states, st.eps, st.m = s_.data_ptr(), None if e is None else e.data_ptr(), M
+        st.action, st.logprob, st.value = action.data_ptr(), logprob.data_ptr(), value.data_ptr()
+        st.states_copy = None if states_copy is None else states_copy.data_ptr()
     if len(value_jobs) > 2:
         raise RlxError("at most two value jobs per launch")
     keep = []
@@ -1154,7 +1036,8 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
                     raise RlxError("value job: flags must be a bool tensor shaped like rewards")
         keep += [js, flags]
         vj = st.value_jobs[k]
-        vj.states, vj.m, vj.values, vj.rewards, vj.flags = js.data_ptr(), m, _ptr(vals), _ptr(rew), _ptr(flags)
+        vj.states, vj.m = js.data_ptr(), m
+        vj.values, vj.rewards, vj.flags = (None if t is None else t.data_ptr() for t in (vals, rew, flags))
         vj.chunk, vj.gamma = chunk, float(j.get("gamma", 1.0))
         if env is not None:
             if rew is None:
@@ -1169,8 +1052,7 @@ def mlp_rollout_step(params: torch.Tensor, tiles: torch.Tensor, layout: MlpLayou
             vj.done_row, vj.termination_row, vj.truncation_row = (t.data_ptr() for t in rows)
             vj.flag_is_truncation = int(bool(j.get("flag_is_truncation", False)))
     st.n_value_jobs = len(value_jobs)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_mlp_rollout_step(byref(st), _stream_ptr(dev)), "rlx_mlp_rollout_step")
+    _lib.launch("rlx_mlp_rollout_step", dev, st)
     return action, logprob, value
 
 
@@ -1196,19 +1078,20 @@ def _ppo_step_args(params, layout, loss, mbatch, grads, out_row, workspace, grad
     has_critic = bool(loss.has_critic)
     a.prev_values = mbatch["prev_values"].data_ptr() if has_critic else None
     a.returns = mbatch["returns"].data_ptr() if has_critic else None
-    lm = mbatch.get("loss_mask")
+    lm, lms = mbatch.get("loss_mask"), mbatch.get("loss_mask_sum")
     a.loss_mask = None if lm is None else lm.data_ptr()
-    a.loss_mask_sum = _ptr(mbatch.get("loss_mask_sum"))
+    a.loss_mask_sum = None if lms is None else lms.data_ptr()
     a.m, a.grad_out = st.shape[0], float(grad_out)
     a.grads, a.slabs, a.out = grads.data_ptr(), grads.shape[0], out_row.data_ptr()
     a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    a.tiles, a.bf16 = _ptr(tiles), int(bool(bf16))
+    a.tiles, a.bf16 = None if tiles is None else tiles.data_ptr(), int(bool(bf16))
     if tiles is not None and (tiles.dtype == torch.bfloat16) != bool(bf16):
         raise RlxError("ppo_step: the tile image's dtype does not match the requested precision")
     if decoupled is not None:  # dict(params=DecoupledLossParams, proximal_logprobs, versions, current_version_dev): see decoupled_step_args
         a.decoupled = ctypes.addressof(decoupled["params"])
-        a.proximal_logprobs, a.versions = _ptr(decoupled.get("proximal_logprobs")), _ptr(decoupled.get("versions"))
-        a.current_version_dev = _ptr(decoupled.get("current_version_dev"))
+        for name in ("proximal_logprobs", "versions", "current_version_dev"):
+            if decoupled.get(name) is not None:
+                setattr(a, name, decoupled[name].data_ptr())
     return a
 
 
@@ -1234,8 +1117,7 @@ def ppo_step(params: torch.Tensor, layout: MlpLayout, loss: PpoLossParams, mbatc
     form (include/rlx.h) -- pass ``deferred_actor_scale`` of the row(s) to the AdamW step."""
     dev = params.device
     a = _ppo_step_args(params, layout, loss, mbatch, grads, out_row, workspace, grad_out, tiles, bf16, decoupled)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_ppo_step(byref(a), _stream_ptr(dev)), "rlx_ppo_step")
+    _lib.launch("rlx_ppo_step", dev, a)
 
 
 # --------------------------------------------------------------------------------------------

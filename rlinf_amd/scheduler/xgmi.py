@@ -20,7 +20,6 @@ import torch.distributed as dist
 
 from .. import _lib
 from .._lib import RlxError, XGMI_HANDLE_BYTES, XGMI_MAX_RANKS
-from ..ops import _stream_ptr
 
 
 class XgmiAllReduce:
@@ -109,10 +108,7 @@ class XgmiAllReduce:
         n = inp.shape[-1] if inp.dim() > 1 else inp.numel()
         slabs = inp.numel() // max(n, 1)
         out = torch.empty(n, dtype=torch.float32, device=inp.device) if out is None else out
-        with torch.cuda.device(inp.device):
-            _lib.check(self._lib.rlx_xgmi_allreduce_f32(self._comm, inp.data_ptr(), slabs, out.data_ptr(), n, float(scale),
-                                                        self._ws.data_ptr(), self._ws.numel(), _stream_ptr(inp.device)),
-                       "rlx_xgmi_allreduce_f32")
+        _lib.launch("rlx_xgmi_allreduce_f32", inp.device, self._comm, inp, slabs, out, n, float(scale), self._ws, self._ws.numel())
         return out
 
     def status_ok(self) -> bool:
@@ -123,8 +119,7 @@ class XgmiAllReduce:
     def status_snapshot(self, dst: torch.Tensor) -> torch.Tensor:
         """dst[0] (device f32) = the status word behind everything queued on the current stream; asynchronous, clears nothing.  The
         run-ahead loop appends it to a step's metric vector and calls check_status() only when it arrives non-zero."""
-        with torch.cuda.device(self.ctx.device):
-            _lib.check(self._lib.rlx_xgmi_status_snapshot(self._comm, dst.data_ptr(), _stream_ptr(self.ctx.device)), "rlx_xgmi_status_snapshot")
+        _lib.launch("rlx_xgmi_status_snapshot", self.ctx.device, self._comm, dst)
         return dst
 
     def check_status(self):
@@ -241,7 +236,7 @@ def _validate_one_launch(comm, ctx, n_max: int, g, validate_timeout_ms: int, pro
         if not ok:
             continue
         with torch.cuda.device(dev):
-            step(_stream_ptr(dev))
+            step(torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.synchronize(dev)
         got = scratch[3] * W
         if not comm.status_ok():
@@ -355,10 +350,8 @@ class LocalXgmiGroup:
         for r in range(self.world):
             x = inputs[r]
             n = x.shape[-1]
-            with torch.cuda.stream(self.streams[r]):
-                _lib.check(self._lib.rlx_xgmi_allreduce_f32(self.comms[r], x.data_ptr(), x.numel() // n, outs[r].data_ptr(), n,
-                                                            float(scale), self._ws[r].data_ptr(), self._ws[r].numel(),
-                                                            self.streams[r].cuda_stream), "rlx_xgmi_allreduce_f32")
+            _lib.launch("rlx_xgmi_allreduce_f32", self.device, self.comms[r], x, x.numel() // n, outs[r], n, float(scale), self._ws[r],
+                        self._ws[r].numel(), stream=self.streams[r].cuda_stream)
         for r in range(self.world):
             cur.wait_stream(self.streams[r])
 
@@ -383,12 +376,9 @@ class LocalXgmiGroup:
             if self._permit is not None:
                 p.sync_words = self._permit.data_ptr()
             keep.append(p)
-            with torch.cuda.stream(self.streams[r]):
-                _lib.check(self._lib.rlx_xgmi_clip_adamw_step(self.comms[r], params[r].data_ptr(), grads[r].data_ptr(),
-                                                              grad_flat[r].data_ptr(), exp_avg[r].data_ptr(), exp_avg_sq[r].data_ptr(),
-                                                              n, ctypes.byref(p), stats[r].data_ptr(), step_state[r].data_ptr(),
-                                                              self._ws[r].data_ptr(), self._ws[r].numel(),
-                                                              self.streams[r].cuda_stream), "rlx_xgmi_clip_adamw_step")
+            _lib.launch("rlx_xgmi_clip_adamw_step", self.device, self.comms[r], params[r], grads[r], grad_flat[r], exp_avg[r],
+                        exp_avg_sq[r], n, p, stats[r], step_state[r], self._ws[r], self._ws[r].numel(),
+                        stream=self.streams[r].cuda_stream)
         for r in range(self.world):
             cur.wait_stream(self.streams[r])
         return keep

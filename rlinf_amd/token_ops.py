@@ -10,14 +10,13 @@ from __future__ import annotations
 
 import os
 
-from ctypes import byref
 from typing import Optional
 
 import torch
 
 from . import _lib
 from ._lib import RlxError, TokenLossParams, TokenRows
-from .ops import _as_f32, _as_u8, _dev, _ptr, _stream_ptr, make_ppo_params
+from .ops import _as_f32, _as_u8, _dev, make_ppo_params
 
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
 
@@ -58,10 +57,7 @@ def token_logprob_fwd(logits: torch.Tensor, labels: torch.Tensor, temperature: f
     logprob = torch.empty(lead, dtype=torch.float32, device=dev)
     lse = torch.empty(lead, dtype=torch.float32, device=dev)
     entropy = torch.empty(lead, dtype=torch.float32, device=dev) if with_entropy else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_token_logprob_fwd(x.data_ptr(), lab.data_ptr(), byref(rows), logprob.data_ptr(),
-                                                     _ptr(entropy), lse.data_ptr(), _stream_ptr(dev)),
-                   "rlx_token_logprob_fwd")
+    _lib.launch("rlx_token_logprob_fwd", dev, x, lab, rows, logprob, entropy, lse)
     return logprob, entropy, lse
 
 
@@ -83,11 +79,9 @@ def token_logprob_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Ten
         dss, drs = out.stride(0), out.stride(1)  # dense [bsz, rows, V] or a slice like the logits
     else:
         raise RlxError("d_logits must be contiguous or a [bsz, rows, V] slice like logits")
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_token_logprob_bwd(
-            x.data_ptr(), labels.contiguous().data_ptr(), byref(rows), _as_f32(lse, "lse").data_ptr(),
-            _ptr(_as_f32(entropy, "entropy")), _as_f32(d_logprob, "d_logprob").data_ptr(),
-            _ptr(_as_f32(d_entropy, "d_entropy")), out.data_ptr(), dss, drs, _stream_ptr(dev)), "rlx_token_logprob_bwd")
+    lab, lse_f, ent = labels.contiguous(), _as_f32(lse, "lse"), _as_f32(entropy, "entropy")
+    d_lp, d_ent = _as_f32(d_logprob, "d_logprob"), _as_f32(d_entropy, "d_entropy")
+    _lib.launch("rlx_token_logprob_bwd", dev, x, lab, rows, lse_f, ent, d_lp, d_ent, out, dss, drs)
     return out
 
 
@@ -140,11 +134,7 @@ class _PackedLogprobFn(torch.autograd.Function):
         logprob = torch.zeros((bsz, response_len), dtype=torch.float32, device=dev)   # pad_val 0 of unpack_sequences
         entropy = torch.zeros((bsz, response_len), dtype=torch.float32, device=dev) if with_entropy else None
         lse = torch.empty(n, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().rlx_token_logprob_fwd_packed(x.data_ptr(), lab.data_ptr(), byref(rows), lp_dst.data_ptr(),
-                                                                _ptr(ent_dst if with_entropy else None), logprob.data_ptr(),
-                                                                _ptr(entropy), lse.data_ptr(), _stream_ptr(dev)),
-                       "rlx_token_logprob_fwd_packed")
+        _lib.launch("rlx_token_logprob_fwd_packed", dev, x, lab, rows, lp_dst, ent_dst if with_entropy else None, logprob, entropy, lse)
         ctx.save_for_backward(logits, lab, lse, lp_dst, ent_dst, entropy if with_entropy else lse)
         ctx.cfg = (float(temperature), bool(with_entropy), bool(inplace_grad))
         ctx.out_shape = (int(bsz), int(response_len))
@@ -169,12 +159,9 @@ class _PackedLogprobFn(torch.autograd.Function):
             dss, drs = 0, rows.vocab
         else:
             dss, drs = out.stride(0), out.stride(1)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().rlx_token_logprob_bwd_packed(
-                x.data_ptr(), lab.data_ptr(), byref(rows), lse.data_ptr(), _ptr(entropy if use_ent else None), lp_dst.data_ptr(),
-                _ptr(ent_dst if use_ent else None), _as_f32(d_logprob, "d_logprob").data_ptr(),
-                _ptr(_as_f32(d_entropy, "d_entropy") if use_ent else None), out.data_ptr(), dss, drs, _stream_ptr(dev)),
-                "rlx_token_logprob_bwd_packed")
+        d_lp, d_ent = _as_f32(d_logprob, "d_logprob"), _as_f32(d_entropy, "d_entropy") if use_ent else None
+        _lib.launch("rlx_token_logprob_bwd_packed", dev, x, lab, rows, lse, entropy if use_ent else None, lp_dst,
+                    ent_dst if use_ent else None, d_lp, d_ent, out, dss, drs)
         return out, None, None, None, None, None, None, None, None, None
 
 
@@ -247,13 +234,9 @@ class _TokenLossFn(torch.autograd.Function):
         g_ent = torch.empty((bsz, seq), dtype=torch.float32, device=dev) if needs_gent else None
         row_w = torch.empty((bsz,), dtype=torch.float32, device=dev)
         out = torch.empty((_lib.TOK_OUT_FLOATS,), dtype=torch.float32, device=dev)
-        ws_bytes = lib.rlx_token_loss_workspace_bytes(bsz, seq)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.rlx_token_loss_fwd(logprobs.data_ptr(), old_logprobs.data_ptr(), advantages.data_ptr(),
-                                              _ptr(ref_logprobs), _ptr(entropy), _ptr(loss_mask), bsz, seq, byref(params),
-                                              g_lp.data_ptr(), _ptr(g_ent), row_w.data_ptr(), out.data_ptr(),
-                                              ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_token_loss_fwd")
+        ws = _lib.workspace(dev, lib.rlx_token_loss_workspace_bytes(bsz, seq))
+        _lib.launch("rlx_token_loss_fwd", dev, logprobs, old_logprobs, advantages, ref_logprobs, entropy, loss_mask, bsz, seq, params,
+                    g_lp, g_ent, row_w, out, ws, ws.numel())
         ctx.save_for_backward(g_lp, g_ent if needs_gent else row_w, row_w)
         ctx.needs_gent = needs_gent
         ctx.ent_given = entropy is not None
@@ -262,17 +245,13 @@ class _TokenLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_out):
-        lib = _lib.load()
         g_lp, g_ent, row_w = ctx.saved_tensors
         dev = g_lp.device
         bsz, seq = g_lp.shape
         go = grad_loss.to(dtype=torch.float32).contiguous()
         d_lp = torch.empty_like(g_lp)
         d_ent = torch.empty_like(g_lp) if ctx.needs_gent else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.rlx_token_loss_bwd(g_lp.data_ptr(), g_ent.data_ptr() if ctx.needs_gent else None,
-                                              row_w.data_ptr(), go.data_ptr(), d_lp.data_ptr(), _ptr(d_ent), bsz, seq,
-                                              _stream_ptr(dev)), "rlx_token_loss_bwd")
+        _lib.launch("rlx_token_loss_bwd", dev, g_lp, g_ent if ctx.needs_gent else None, row_w, go, d_lp, d_ent, bsz, seq)
         return d_lp, d_ent, None, None, None, None, None
 
 
@@ -307,9 +286,7 @@ def grpo_seq_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, group_size: int
     r = _as_f32(rewards.reshape(-1), "rewards")
     m = _as_u8(loss_mask)
     adv = torch.empty((bsz, seq), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_grpo_seq_adv(r.data_ptr(), m.data_ptr(), adv.data_ptr(), bsz, seq, int(group_size),
-                                                float(eps), _stream_ptr(dev)), "rlx_grpo_seq_adv")
+    _lib.launch("rlx_grpo_seq_adv", dev, r, m, adv, bsz, seq, int(group_size), float(eps))
     return adv
 
 
@@ -336,13 +313,8 @@ def reinpp_seq_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, logprob: Opti
         if tuple(lp.shape) != (bsz, seq) or tuple(rp.shape) != (bsz, seq):
             raise RlxError("reinpp_seq_adv: logprob / ref_logprob must be [bsz, seq]")
     adv = torch.empty((bsz, seq), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    ws_bytes = lib.rlx_reinpp_workspace_bytes(bsz)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_reinpp_seq_adv(r.data_ptr(), m.data_ptr(), None if lp is None else lp.data_ptr(),
-                                          None if rp is None else rp.data_ptr(), kind, float(kl_beta), adv.data_ptr(), bsz, seq,
-                                          ws.data_ptr(), ws_bytes, _stream_ptr(dev)), "rlx_reinpp_seq_adv")
+    ws = _lib.workspace(dev, _lib.load().rlx_reinpp_workspace_bytes(bsz))
+    _lib.launch("rlx_reinpp_seq_adv", dev, r, m, lp, rp, kind, float(kl_beta), adv, bsz, seq, ws, ws.numel())
     return adv
 
 
@@ -397,13 +369,9 @@ def categorical_sample(logits: torch.Tensor, noise: Optional[torch.Tensor] = Non
     tokens = torch.empty(lead, dtype=torch.int64, device=dev)
     logprob = torch.empty(lead, dtype=torch.float32, device=dev) if with_logprob else None
     actions = torch.empty(lead, dtype=torch.float32, device=dev) if centers is not None else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_categorical_sample(x.data_ptr(), byref(rows), _ptr(noise), int(top_k),
-                                                      int(softmax_lanes if softmax_lanes is not None else default_softmax_lanes()),
-                                                      _ptr(centers),
-                                                      0 if centers is None else centers.numel(), tokens.data_ptr(),
-                                                      _ptr(logprob), _ptr(actions), _stream_ptr(dev)),
-                   "rlx_categorical_sample")
+    lanes = int(softmax_lanes if softmax_lanes is not None else default_softmax_lanes())
+    _lib.launch("rlx_categorical_sample", dev, x, rows, noise, int(top_k), lanes, centers, 0 if centers is None else centers.numel(),
+                tokens, logprob, actions)
     return tokens, logprob, actions
 
 
@@ -417,12 +385,9 @@ def gae_seq(values: torch.Tensor, rewards: torch.Tensor, gamma: float = 1.0, gae
     r = _as_f32(rewards.reshape(-1), "rewards")
     bsz, seq = v.shape
     adv, ret = (torch.empty_like(v), torch.empty_like(v)) if out is None else out
-    lib = _lib.load()
-    wsb = lib.rlx_gae_seq_workspace_bytes(bsz, seq)
-    ws = workspace if workspace is not None and workspace.numel() >= wsb else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.rlx_gae_seq(v.data_ptr(), r.data_ptr(), adv.data_ptr(), ret.data_ptr(), bsz, seq, float(gamma),
-                                   float(gamma * gae_lambda), ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "rlx_gae_seq")
+    wsb = _lib.load().rlx_gae_seq_workspace_bytes(bsz, seq)
+    ws = workspace if workspace is not None and workspace.numel() >= wsb else _lib.workspace(dev, wsb)
+    _lib.launch("rlx_gae_seq", dev, v, r, adv, ret, bsz, seq, float(gamma), float(gamma * gae_lambda), ws, ws.numel())
     return adv, ret
 
 
@@ -498,11 +463,8 @@ def grpo_dynamic_adv(rewards: torch.Tensor, loss_mask: torch.Tensor, plan: GrpoD
         m = m.clone()
     num_seq, seq = loss_mask.shape
     adv = torch.empty((num_seq, seq), dtype=rewards.dtype, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_grpo_dynamic_adv(r.data_ptr(), _DTYPES[r.dtype], plan.plan.data_ptr(), m.data_ptr(),
-                                                    adv.data_ptr(), num_seq, plan.num_traj, seq, plan.group_size,
-                                                    _lib.GRPO_DYN_MODES[mode], float(eps), _stream_ptr(dev)),
-                   "rlx_grpo_dynamic_adv")
+    _lib.launch("rlx_grpo_dynamic_adv", dev, r, _DTYPES[r.dtype], plan.plan, m, adv, num_seq, plan.num_traj, seq, plan.group_size,
+                _lib.GRPO_DYN_MODES[mode], float(eps))
     return adv
 
 
@@ -565,9 +527,7 @@ def scale_rows_(x: torch.Tensor, factor: float = 1.0, row_factors: Optional[torc
             raise RlxError("scale_rows_: row_factors must be f32 [x.shape[0]]")
         rows, cols = x.shape[0], (x.numel() // x.shape[0] if x.shape[0] else 0)
         row_factors = row_factors.contiguous()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_loss_scale_rows(x.data_ptr(), dt, _ptr(row_factors), float(factor), rows, cols,
-                                                   _stream_ptr(dev)), "rlx_loss_scale_rows")
+    _lib.launch("rlx_loss_scale_rows", dev, x, dt, row_factors, float(factor), rows, cols)
     return x
 
 
@@ -592,8 +552,6 @@ def turn_level_scale_(loss_scales: torch.Tensor, response_mask: torch.Tensor, pl
     m = _as_u8(response_mask)
     if m.data_ptr() % 4:
         m = m.clone()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rlx_loss_scale_turn(loss_scales.data_ptr(), dt, m.data_ptr(), plan.plan.data_ptr(), plan.num_seq,
-                                                   plan.num_groups, loss_scales.shape[1], plan.zero_flag.data_ptr(),
-                                                   _stream_ptr(dev)), "rlx_loss_scale_turn")
+    _lib.launch("rlx_loss_scale_turn", dev, loss_scales, dt, m, plan.plan, plan.num_seq, plan.num_groups, loss_scales.shape[1],
+                plan.zero_flag)
     return plan.zero_flag

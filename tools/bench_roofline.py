@@ -265,7 +265,6 @@ def token_tier_roofline(device, tokens: int = 4096, vocab: int = 151936, iters: 
         return rows
     try:
         from rlinf_amd import _lib
-        from rlinf_amd.ops import _stream_ptr
         lib = _lib.load()
         n = 100_000_000
         streams = (("rows: uint8 deltas, 1 in 800 nonzero", (torch.rand(n, device=device, generator=g) < 1 / 800).to(torch.uint8)),
@@ -276,13 +275,10 @@ def token_tier_roofline(device, tokens: int = 4096, vocab: int = 151936, iters: 
             ws = torch.empty(lib.rlx_zplane_workspace_bytes(ne, es), dtype=torch.uint8, device=device)
             length = torch.zeros(1, dtype=torch.int64, device=device)
             back, status = torch.empty_like(t), torch.zeros(1, dtype=torch.int32, device=device)
-            st = _stream_ptr(dev_t)
-            comp = lambda: _lib.check(lib.rlx_zplane_compress(t.data_ptr(), ne, es, out.data_ptr(), out.numel(), length.data_ptr(),  # noqa: E731
-                                                              ws.data_ptr(), ws.numel(), st), "rlx_zplane_compress")
+            comp = lambda: _lib.launch("rlx_zplane_compress", dev_t, t, ne, es, out, out.numel(), length, ws, ws.numel())  # noqa: E731
             t_c = avg_us(comp)
             clen = int(length.item())
-            dec = lambda: _lib.check(lib.rlx_zplane_decompress(out.data_ptr(), clen, back.data_ptr(), ne, es, status.data_ptr(), st),  # noqa: E731
-                                     "rlx_zplane_decompress")
+            dec = lambda: _lib.launch("rlx_zplane_decompress", dev_t, out, clen, back, ne, es, status)  # noqa: E731
             t_d = avg_us(dec)
             ok = bool(torch.equal(back, t)) and int(status.item()) == 0
             raw = ne * es
