@@ -1,5 +1,5 @@
 """Built-in policy losses behind the registry names "actor_critic", "actor", "decoupled_actor_critic" and "opd"
-(mirror of rlinf/algorithms/losses.py:27-167,170-380,383-535), served by ppo_loss.hip / decoupled_loss.hip / token_ops.hip /
+(mirror of rlinf/algorithms/losses.py:27-167,170-380,383-535), served by ppo_loss.hip (classic and decoupled) / token_ops.hip /
 opd.hip.
 
 ``policy_loss(**kwargs)`` in the reference runs preprocess_loss_inputs, the loss, and then ``.item()``

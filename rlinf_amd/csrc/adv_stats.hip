@@ -14,8 +14,6 @@
 namespace rlx {
 namespace {
 
-constexpr int kStatBlocks = 1024;
-
 __global__ __launch_bounds__(256) void masked_stats_partial_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m,
                                                                    long long n, double* __restrict__ partials) {
     __shared__ double s_red[3 * 4];
@@ -26,21 +24,13 @@ __global__ __launch_bounds__(256) void masked_stats_partial_kernel(const float* 
         const double v = (double)x[i];
         if (on) acc[0] += 1.0, acc[1] += v, acc[2] += v * v;
     }
-    block_sum<3>(acc, s_red);
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x * 3 + 0] = acc[0];
-        partials[blockIdx.x * 3 + 1] = acc[1];
-        partials[blockIdx.x * 3 + 2] = acc[2];
-    }
+    store_partials<3>(acc, s_red, partials);
 }
 __global__ __launch_bounds__(256) void masked_stats_final_kernel(const double* __restrict__ partials, int nparts,
                                                                  double* __restrict__ stats, int accumulate) {
     __shared__ double s_red[3 * 4];
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        acc[0] += partials[i * 3], acc[1] += partials[i * 3 + 1], acc[2] += partials[i * 3 + 2];
-    }
-    block_sum<3>(acc, s_red);
+    double acc[3];
+    fold_partials<3>(partials, nparts, acc, s_red);
     if (threadIdx.x == 0) {
         for (int k = 0; k < 3; ++k) stats[k] = accumulate ? stats[k] + acc[k] : acc[k];
     }
@@ -104,18 +94,11 @@ __global__ __launch_bounds__(256) void rollout_metrics_partial_kernel(MetricArgs
         }
         block_sum<2>(sum, s_red);
         __syncthreads();
-        // min / max: wave shuffles, then through LDS
-        for (int off = 32; off > 0; off >>= 1) {
-            lo = fminf(lo, __shfl_xor(lo, off, RLX_WAVE));
-            hi = fmaxf(hi, __shfl_xor(hi, off, RLX_WAVE));
-        }
-        float* s_mm = reinterpret_cast<float*>(s_red + 8);
-        if ((threadIdx.x & 63) == 0) s_mm[(threadIdx.x >> 6) * 2] = lo, s_mm[(threadIdx.x >> 6) * 2 + 1] = hi;
-        __syncthreads();
+        float mm[2] = {-lo, hi};  // (-min, max), the form the row carries
+        block_max(mm, reinterpret_cast<float*>(s_red + 8));
         if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w) lo = fminf(lo, s_mm[w * 2]), hi = fmaxf(hi, s_mm[w * 2 + 1]);
             double* p = partials + ((size_t)blockIdx.x * kMetricArrays + k) * 4;
-            p[0] = sum[0], p[1] = sum[1], p[2] = (double)-lo, p[3] = (double)hi;
+            p[0] = sum[0], p[1] = sum[1], p[2] = (double)mm[0], p[3] = (double)mm[1];
         }
         __syncthreads();
     }
@@ -124,35 +107,23 @@ __global__ __launch_bounds__(256) void rollout_metrics_final_kernel(const double
                                                                     double* __restrict__ out) {
     __shared__ double s_red[2 * 4];
     __shared__ double s_mm[2 * 4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int k = 0; k < count; ++k) {
         double sum[2] = {0.0, 0.0};
-        double nlo = -INFINITY, hi = -INFINITY;
+        double mm[2] = {-INFINITY, -INFINITY};  // (-min, max)
         for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
             const double* p = partials + ((size_t)i * kMetricArrays + k) * 4;
             sum[0] += p[0], sum[1] += p[1];
-            nlo = fmax(nlo, p[2]), hi = fmax(hi, p[3]);
+            mm[0] = fmax(mm[0], p[2]), mm[1] = fmax(mm[1], p[3]);
         }
         block_sum<2>(sum, s_red);
         // max is order-independent: a wave butterfly + four wave results (thread 0 used to walk 256 LDS pairs one after the other:
         // 17 us for a launch that reduces a few hundred numbers)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            nlo = fmax(nlo, __shfl_xor(nlo, off, 64));
-            hi = fmax(hi, __shfl_xor(hi, off, 64));
-        }
-        if (lane == 0) s_mm[wave * 2] = nlo, s_mm[wave * 2 + 1] = hi;
-        __syncthreads();
+        block_max(mm, s_mm);
         if (threadIdx.x == 0) {
-            for (int t = 1; t < (int)(blockDim.x >> 6); ++t) nlo = fmax(nlo, s_mm[t * 2]), hi = fmax(hi, s_mm[t * 2 + 1]);
-            out[k * 4 + 0] = sum[0], out[k * 4 + 1] = sum[1], out[k * 4 + 2] = nlo, out[k * 4 + 3] = hi;
+            out[k * 4 + 0] = sum[0], out[k * 4 + 1] = sum[1], out[k * 4 + 2] = mm[0], out[k * 4 + 3] = mm[1];
         }
         __syncthreads();
     }
-}
-
-int stat_grid(long long n) {
-    return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, std::min<long long>(kStatBlocks, (long long)num_cu() * 4)));
 }
 
 }  // namespace
@@ -162,20 +133,17 @@ using namespace rlx;
 
 extern "C" size_t rlx_masked_stats_workspace_bytes(int64_t n) {
     (void)n;
-    return (size_t)kStatBlocks * 3 * sizeof(double);
+    return (size_t)kPartialBlocks * 3 * sizeof(double);
 }
 
 extern "C" int rlx_masked_stats(const float* x, const uint8_t* mask, int64_t n, double* stats, int accumulate, void* workspace,
                                 size_t workspace_bytes, rlx_stream_t stream) {
     RLX_REQUIRE(n >= 0 && stats && workspace, "rlx_masked_stats: bad argument");
     RLX_REQUIRE(n == 0 || x, "rlx_masked_stats: NULL x");
-    if (workspace_bytes < rlx_masked_stats_workspace_bytes(n)) {
-        set_error("rlx_masked_stats: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_masked_stats_workspace_bytes(n), "rlx_masked_stats");
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* partials = static_cast<double*>(workspace);
-    const int nblk = n > 0 ? stat_grid(n) : 1;
+    const int nblk = n > 0 ? stream_grid(n) : 1;
     hipLaunchKernelGGL(masked_stats_partial_kernel, dim3(nblk), dim3(256), 0, s, x, mask, (long long)n, partials);
     RLX_LAUNCH_CHECK();
     hipLaunchKernelGGL(masked_stats_final_kernel, dim3(1), dim3(256), 0, s, partials, nblk, stats, accumulate);
@@ -187,7 +155,7 @@ extern "C" int rlx_normalize_from_stats(const float* x, const double* stats, flo
     RLX_REQUIRE(n >= 0 && stats, "rlx_normalize_from_stats: bad argument");
     if (n == 0) return RLX_OK;
     RLX_REQUIRE(x && out, "rlx_normalize_from_stats: NULL argument");
-    hipLaunchKernelGGL(normalize_from_stats_kernel, dim3(stat_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, stats,
+    hipLaunchKernelGGL(normalize_from_stats_kernel, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, stats,
                        out, (long long)n);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
@@ -198,7 +166,7 @@ extern "C" int rlx_masked_normalize(const float* x, const uint8_t* mask, const d
     RLX_REQUIRE(n >= 0 && stats, "rlx_masked_normalize: bad argument");
     if (n == 0) return RLX_OK;
     RLX_REQUIRE(x && out, "rlx_masked_normalize: NULL argument");
-    hipLaunchKernelGGL(masked_normalize_kernel, dim3(stat_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, mask, stats,
+    hipLaunchKernelGGL(masked_normalize_kernel, dim3(stream_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, mask, stats,
                        eps, out, (long long)n);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
@@ -209,10 +177,7 @@ extern "C" size_t rlx_rollout_metrics_workspace_bytes(void) { return (size_t)256
 extern "C" int rlx_rollout_metrics(const float* const* arrays, const int64_t* sizes, int count, const uint8_t* mask,
                                    int64_t mask_elems, double* out, void* workspace, size_t workspace_bytes, rlx_stream_t stream) {
     RLX_REQUIRE(arrays && sizes && out && workspace && count >= 1 && count <= kMetricArrays, "rlx_rollout_metrics: bad argument");
-    if (workspace_bytes < rlx_rollout_metrics_workspace_bytes()) {
-        set_error("rlx_rollout_metrics: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_rollout_metrics_workspace_bytes(), "rlx_rollout_metrics");
     MetricArgs a{};
     a.count = count;
     long long nmax = 0;

@@ -681,10 +681,7 @@ extern "C" int rlx_masked_standardize(float* x, const uint8_t* mask, size_t n, f
     RLX_REQUIRE(x != nullptr || n == 0, "rlx_masked_standardize: NULL x");
     if (n == 0) return RLX_OK;
     RLX_REQUIRE(workspace != nullptr, "rlx_masked_standardize: NULL workspace");
-    if (workspace_bytes < rlx_standardize_workspace_bytes(n)) {
-        set_error("rlx_masked_standardize: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_standardize_workspace_bytes(n), "rlx_masked_standardize");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nblk = (int)std::max<long long>(1, std::min<long long>((long long)((n + 255) / 256), std::min(kMaxParts, num_cu() * 8)));
     double* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + kNormWords * 8);

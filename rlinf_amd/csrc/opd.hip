@@ -24,7 +24,6 @@ namespace rlx {
 namespace {
 
 constexpr int kOpdAcc = 3;  // sum(v*m) or sum((v/ratio)*m), sum(adv*m), sum(m)
-constexpr int kMaxOpdBlocks = 1024;
 
 template <typename T>
 struct Vec4 {
@@ -113,22 +112,14 @@ __global__ __launch_bounds__(256) void opd_loss_fwd_kernel(OpdLossArgs a, double
     } else {
         for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < a.n; e += stride) opd_elem(a, e, a.lp[e], a.adv[e], acc);
     }
-    block_sum<kOpdAcc>(acc, s_red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < kOpdAcc; ++k) partials[(size_t)blockIdx.x * kOpdAcc + k] = acc[k];
-    }
+    store_partials<kOpdAcc>(acc, s_red, partials);
 }
 
 __global__ __launch_bounds__(256) void opd_loss_finalize(const double* __restrict__ partials, int nparts, long long n,
                                                          int ratio_mode, float* __restrict__ out) {
     __shared__ double s_red[kOpdAcc * 4];
-    double acc[kOpdAcc] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < kOpdAcc; ++k) acc[k] += partials[(size_t)i * kOpdAcc + k];
-    }
-    block_sum<kOpdAcc>(acc, s_red);
+    double acc[kOpdAcc];
+    fold_partials<kOpdAcc>(partials, nparts, acc, s_red);
     if (threadIdx.x != 0) return;
     const double cnt = acc[2];
     // masked_mean over an all-False mask is the masked SUM (utils.py:326-327); masked_mean_ratio is a plain mean
@@ -170,11 +161,6 @@ __global__ __launch_bounds__(256) void opd_loss_bwd_kernel(OpdLossArgs a, const 
     }
 }
 
-int opd_grid(long long work) {
-    const long long want = (work + 255) / 256;
-    return (int)std::max<long long>(1, std::min<long long>(want, std::min<long long>(kMaxOpdBlocks, (long long)num_cu() * 4)));
-}
-
 template <typename TT, typename PT>
 void launch_adv(const void* teacher, const void* prev, float* out, long long rows, long long inner, long long ts, long long ps,
                 hipStream_t s) {
@@ -183,8 +169,8 @@ void launch_adv(const void* teacher, const void* prev, float* out, long long row
                      reinterpret_cast<uintptr_t>(prev) % (4 * sizeof(PT)) == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
     const TT* t = static_cast<const TT*>(teacher);
     const PT* p = static_cast<const PT*>(prev);
-    if (vec) hipLaunchKernelGGL((opd_adv_kernel<TT, PT, true>), dim3(opd_grid(rows * inner / 4)), dim3(256), 0, s, t, p, out, rows, inner, ts, ps);
-    else hipLaunchKernelGGL((opd_adv_kernel<TT, PT, false>), dim3(opd_grid(rows * inner)), dim3(256), 0, s, t, p, out, rows, inner, ts, ps);
+    if (vec) hipLaunchKernelGGL((opd_adv_kernel<TT, PT, true>), dim3(stream_grid(rows * inner / 4)), dim3(256), 0, s, t, p, out, rows, inner, ts, ps);
+    else hipLaunchKernelGGL((opd_adv_kernel<TT, PT, false>), dim3(stream_grid(rows * inner)), dim3(256), 0, s, t, p, out, rows, inner, ts, ps);
 }
 
 template <typename TT>
@@ -252,7 +238,7 @@ extern "C" int rlx_opd_advantages(const void* teacher, int teacher_dtype, int64_
 
 extern "C" size_t rlx_opd_loss_workspace_bytes(int64_t n) {
     (void)n;
-    return (size_t)kMaxOpdBlocks * kOpdAcc * sizeof(double);
+    return (size_t)kPartialBlocks * kOpdAcc * sizeof(double);
 }
 
 extern "C" int rlx_opd_loss_fwd(const float* logprobs, const float* advantages, const uint8_t* loss_mask, int mask_div,
@@ -262,16 +248,13 @@ extern "C" int rlx_opd_loss_fwd(const float* logprobs, const float* advantages, 
                                    max_episode_steps, "rlx_opd_loss_fwd");
     if (rc != RLX_OK) return rc;
     RLX_REQUIRE(out != nullptr && workspace != nullptr, "rlx_opd_loss_fwd: NULL out / workspace");
-    if (workspace_bytes < rlx_opd_loss_workspace_bytes(n)) {
-        set_error("rlx_opd_loss_fwd: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_opd_loss_workspace_bytes(n), "rlx_opd_loss_fwd");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const OpdLossArgs a = make_args(logprobs, advantages, loss_mask, loss_mask_sum, n, mask_div, msum_div, msum_i64,
                                     max_episode_steps);
     double* partials = static_cast<double*>(workspace);
     const bool vec = vec4_ok(logprobs, advantages, n);
-    const int nblk = opd_grid(vec ? n / 4 : n);
+    const int nblk = stream_grid(vec ? n / 4 : n);
     if (vec) hipLaunchKernelGGL(opd_loss_fwd_kernel<true>, dim3(nblk), dim3(256), 0, s, a, partials);
     else hipLaunchKernelGGL(opd_loss_fwd_kernel<false>, dim3(nblk), dim3(256), 0, s, a, partials);
     RLX_LAUNCH_CHECK();
@@ -294,8 +277,8 @@ extern "C" int rlx_opd_loss_bwd(const float* advantages, const uint8_t* loss_mas
     const OpdLossArgs a = make_args(nullptr, advantages, loss_mask, loss_mask_sum, n, mask_div, msum_div, msum_i64,
                                     max_episode_steps);
     const bool vec = vec4_ok(advantages, d_logprobs, n);
-    if (vec) hipLaunchKernelGGL(opd_loss_bwd_kernel<true>, dim3(opd_grid(n / 4)), dim3(256), 0, s, a, out, grad_out, d_logprobs);
-    else hipLaunchKernelGGL(opd_loss_bwd_kernel<false>, dim3(opd_grid(n)), dim3(256), 0, s, a, out, grad_out, d_logprobs);
+    if (vec) hipLaunchKernelGGL(opd_loss_bwd_kernel<true>, dim3(stream_grid(n / 4)), dim3(256), 0, s, a, out, grad_out, d_logprobs);
+    else hipLaunchKernelGGL(opd_loss_bwd_kernel<false>, dim3(stream_grid(n)), dim3(256), 0, s, a, out, grad_out, d_logprobs);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -1,4 +1,5 @@
-// ppo_loss.hip -- fused PPO clipped-surrogate + clipped-Huber value loss, forward and backward, gfx950.
+// ppo_loss.hip -- fused PPO clipped-surrogate + clipped-Huber value loss, classic and decoupled (asynchronous), forward and
+// backward, gfx950.
 //
 // Replaces (after rlinf/algorithms/utils.py:280-376 preprocess_loss_inputs):
 //   compute_ppo_actor_loss   rlinf/algorithms/losses.py:170-312
@@ -23,32 +24,33 @@ namespace {
 
 using namespace loss;
 
+// One argument block for both losses; prox / versions and the fields of p behind p.ppo are read by the decoupled form only.
 struct LossArgs {
-    const float* lp;
-    const float* old;
-    const float* adv;
-    const float* v;
-    const float* pv;
-    const float* ret;
+    const float *lp, *old, *prox, *versions, *adv, *v, *pv, *ret;
     const uint8_t* m;
     const int64_t* msum;
-    float* g_lp;
-    float* g_v;
+    float *g_lp, *g_v;
     double* partials;
     long long n;
-    rlx_ppo_loss_params p;
+    rlx_decoupled_loss_params p;
 };
 
-template <bool VEC4>
+// reduction slots: ppo_loss_math.h; the decoupled rows carry one more, the version sum
+constexpr int slots(bool decoupled) { return NS + (decoupled ? 1 : 0); }
+
+template <bool DECOUPLED, bool VEC4>
 __global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(LossArgs a) {
-    __shared__ double s_red[NS * 4];
-    const rlx_ppo_loss_params& p = a.p;
+    constexpr int N = slots(DECOUPLED);
+    __shared__ double s_red[N * 4];
+    const rlx_ppo_loss_params& p = a.p.ppo;
     const int K = p.raw_per_adv, S = p.sub_per_adv, R = K / S;
     const bool ratio_mode = p.max_episode_steps > 0 && a.m != nullptr && a.msum != nullptr;
     const float half_delta = (float)(0.5 * (double)p.huber_delta);
-    double acc[NS];
+    const DecoupledMode dm{a.p.proximal_mode, a.p.use_behave_threshold, a.p.behave_weight_threshold, a.p.current_version};
+    const bool given = DECOUPLED && dm.mode == RLX_PROX_GIVEN;
+    double acc[N];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
 
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < a.n; e += stride) {
@@ -59,10 +61,15 @@ __global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(LossArgs a) {
         acc[S_NM] += on ? 1.0 : 0.0;
         const float* lpp = a.lp + e * K;
         const float* olp = a.old + e * K;
+        const float* pxp = given ? a.prox + e * K : nullptr;
         for (int s = 0; s < S; ++s) {
-            float lp = 0.f, old = 0.f;
-            if constexpr (VEC4) {
+            float lp = 0.f, old = 0.f, px = 0.f;
+            if constexpr (VEC4) {  // the same element order as the scalar loop: the same bits
                 for (int j = 0; j < R; j += 4) {
+                    if (given) {  // (in front of the other two: 80 VGPRs, the scalar form's occupancy step; behind them 82)
+                        const float4 z = *reinterpret_cast<const float4*>(pxp + s * R + j);
+                        px = fadd(fadd(fadd(fadd(px, z.x), z.y), z.z), z.w);
+                    }
                     const float4 x = *reinterpret_cast<const float4*>(lpp + s * R + j);
                     const float4 y = *reinterpret_cast<const float4*>(olp + s * R + j);
                     lp = fadd(fadd(fadd(fadd(lp, x.x), x.y), x.z), x.w);
@@ -72,37 +79,39 @@ __global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(LossArgs a) {
                 for (int j = 0; j < R; ++j) {
                     lp = fadd(lp, lpp[s * R + j]);
                     old = fadd(old, olp[s * R + j]);
+                    if (given) px = fadd(px, pxp[s * R + j]);
                 }
             }
-            const float g = actor_elem(p, lp, old, adv, on, w, ratio_mode, acc);
+            float g;
+            if constexpr (DECOUPLED) {
+                const float vb = a.versions ? a.versions[e * K + s * R] : 0.f;  // the slice's first entry (utils.py:337,348)
+                g = decoupled_actor_elem(p, dm, lp, old, px, vb, adv, on, w, ratio_mode, acc, NS);
+            } else {
+                g = actor_elem(p, lp, old, adv, on, w, ratio_mode, acc);
+            }
             a.g_lp[e * S + s] = g;
         }
-        if (p.has_critic) {
-            const float gv = critic_elem(p, a.v[e], a.pv[e], a.ret[e], on, w, ratio_mode, half_delta, acc);
-            a.g_v[e] = gv;
-        }
+        if (p.has_critic) a.g_v[e] = critic_elem(p, a.v[e], a.pv[e], a.ret[e], on, w, ratio_mode, half_delta, acc);
     }
-    block_sum<NS>(acc, s_red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) a.partials[(size_t)blockIdx.x * NS + k] = acc[k];
-    }
+    store_partials<N>(acc, s_red, a.partials);
 }
 
+template <bool DECOUPLED>
 __global__ __launch_bounds__(256) void ppo_loss_finalize(const double* partials, int nparts, long long n_adv,
-                                                         rlx_ppo_loss_params p, int has_mask, int has_msum,
-                                                         float* out) {
-    __shared__ double s_red[NS * 4];
-    double acc[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) acc[k] = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) acc[k] += partials[(size_t)i * NS + k];
-    }
-    block_sum<NS>(acc, s_red);
+                                                         rlx_decoupled_loss_params dp, int has_mask, int has_msum, float* out) {
+    constexpr int N = slots(DECOUPLED);
+    __shared__ double s_red[N * 4];
+    double acc[N];
+    fold_partials<N>(partials, nparts, acc, s_red);
     if (threadIdx.x != 0) return;
-    finalize_row(p, n_adv, has_mask != 0, has_msum != 0, acc, out);
+    if constexpr (DECOUPLED) {
+        double main[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) main[k] = acc[k];
+        finalize_row_decoupled(dp.ppo, dp.use_behave_threshold != 0, n_adv, has_mask != 0, has_msum != 0, main, acc[NS], out);
+    } else {
+        finalize_row(dp.ppo, n_adv, has_mask != 0, has_msum != 0, acc, out);
+    }
 }
 
 __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* g_lp, const float* g_v, const float* out,
@@ -148,11 +157,40 @@ __global__ __launch_bounds__(64) void entropy_bonus_kernel(const float* __restri
     }
 }
 
-constexpr int kMaxLossBlocks = 1024;
+size_t loss_workspace_bytes(bool decoupled) { return (size_t)kPartialBlocks * slots(decoupled) * sizeof(double); }
 
-int loss_grid(long long n) {
-    const long long want = (n + 255) / 256;
-    return (int)std::max<long long>(1, std::min<long long>(want, std::min<long long>(kMaxLossBlocks, (long long)num_cu() * 4)));
+// What the two forward entry points share: the checks on the common arguments (in `who`'s name) and the two launches.
+int loss_fwd(const char* who, bool decoupled, LossArgs& a, float* out, void* workspace, size_t workspace_bytes, rlx_stream_t stream) {
+    const rlx_ppo_loss_params* p = &a.p.ppo;
+    RLX_REQUIRE(a.n >= 0, "%s: negative size", who);
+    RLX_REQUIRE(p->raw_per_adv >= 1 && p->sub_per_adv >= 1 && p->raw_per_adv % p->sub_per_adv == 0,
+                "%s: raw_per_adv=%d must be a positive multiple of sub_per_adv=%d", who, p->raw_per_adv, p->sub_per_adv);
+    RLX_REQUIRE(a.n == 0 || (a.lp && a.old && a.adv && a.g_lp), "%s: NULL actor argument", who);
+    RLX_REQUIRE(!p->has_critic || a.n == 0 || (a.v && a.pv && a.ret && a.g_v), "%s: has_critic set but a critic tensor is NULL", who);
+    RLX_REQUIRE(!p->use_dual_clip || p->clip_ratio_c > 1.0f, "clip_ratio_c must be greater than 1.0");  // losses.py:108,262
+    RLX_REQUIRE(workspace != nullptr, "%s: NULL workspace", who);
+    RLX_REQUIRE_SPACE(workspace_bytes, loss_workspace_bytes(decoupled), who);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    a.partials = static_cast<double*>(workspace);
+    const int nblk = stream_grid(a.n);
+    const int R = p->raw_per_adv / p->sub_per_adv;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(a.lp) | reinterpret_cast<uintptr_t>(a.old);
+    if (decoupled && a.p.proximal_mode == RLX_PROX_GIVEN) bits |= reinterpret_cast<uintptr_t>(a.prox);
+    const bool vec4 = R % 4 == 0 && bits % 16 == 0;
+    const int has_mask = a.m != nullptr ? 1 : 0, has_msum = a.msum != nullptr ? 1 : 0;
+    if (decoupled) {
+        if (vec4) hipLaunchKernelGGL((ppo_loss_fwd_kernel<true, true>), dim3(nblk), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((ppo_loss_fwd_kernel<true, false>), dim3(nblk), dim3(256), 0, s, a);
+        RLX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ppo_loss_finalize<true>, dim3(1), dim3(256), 0, s, a.partials, nblk, a.n, a.p, has_mask, has_msum, out);
+    } else {
+        if (vec4) hipLaunchKernelGGL((ppo_loss_fwd_kernel<false, true>), dim3(nblk), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((ppo_loss_fwd_kernel<false, false>), dim3(nblk), dim3(256), 0, s, a);
+        RLX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ppo_loss_finalize<false>, dim3(1), dim3(256), 0, s, a.partials, nblk, a.n, a.p, has_mask, has_msum, out);
+    }
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
 }
 
 }  // namespace
@@ -162,7 +200,12 @@ using namespace rlx;
 
 extern "C" size_t rlx_ppo_loss_workspace_bytes(int64_t n_adv) {
     (void)n_adv;
-    return (size_t)kMaxLossBlocks * NS * sizeof(double);
+    return loss_workspace_bytes(false);
+}
+
+extern "C" size_t rlx_decoupled_loss_workspace_bytes(int64_t n_adv) {
+    (void)n_adv;
+    return loss_workspace_bytes(true);
 }
 
 extern "C" int rlx_ppo_loss_fwd(const float* logprobs, const float* old_logprobs, const float* advantages,
@@ -171,35 +214,33 @@ extern "C" int rlx_ppo_loss_fwd(const float* logprobs, const float* old_logprobs
                                 const rlx_ppo_loss_params* p, float* g_logp, float* g_value, float* out, void* workspace,
                                 size_t workspace_bytes, rlx_stream_t stream) {
     RLX_REQUIRE(p != nullptr && out != nullptr, "rlx_ppo_loss_fwd: NULL params/out");
-    RLX_REQUIRE(n_adv >= 0, "rlx_ppo_loss_fwd: negative size");
-    RLX_REQUIRE(p->raw_per_adv >= 1 && p->sub_per_adv >= 1 && p->raw_per_adv % p->sub_per_adv == 0,
-                "rlx_ppo_loss_fwd: raw_per_adv=%d must be a positive multiple of sub_per_adv=%d", p->raw_per_adv,
-                p->sub_per_adv);
-    RLX_REQUIRE(n_adv == 0 || (logprobs && old_logprobs && advantages && g_logp), "rlx_ppo_loss_fwd: NULL actor argument");
-    RLX_REQUIRE(!p->has_critic || n_adv == 0 || (values && prev_values && returns && g_value),
-                "rlx_ppo_loss_fwd: has_critic set but a critic tensor is NULL");
-    RLX_REQUIRE(!p->use_dual_clip || p->clip_ratio_c > 1.0f, "clip_ratio_c must be greater than 1.0");  // losses.py:262
-    RLX_REQUIRE(workspace != nullptr, "rlx_ppo_loss_fwd: NULL workspace");
-    if (workspace_bytes < rlx_ppo_loss_workspace_bytes(n_adv)) {
-        set_error("rlx_ppo_loss_fwd: workspace too small");
-        return RLX_ENOSPC;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    LossArgs a;
-    a.lp = logprobs; a.old = old_logprobs; a.adv = advantages; a.v = values; a.pv = prev_values; a.ret = returns;
-    a.m = loss_mask; a.msum = loss_mask_sum; a.g_lp = g_logp; a.g_v = g_value;
-    a.partials = static_cast<double*>(workspace);
-    a.n = n_adv; a.p = *p;
-    const int nblk = loss_grid(n_adv);
-    const int R = p->raw_per_adv / p->sub_per_adv;
-    const bool vec4 = R % 4 == 0 && (reinterpret_cast<uintptr_t>(logprobs) | reinterpret_cast<uintptr_t>(old_logprobs)) % 16 == 0;
-    if (vec4) hipLaunchKernelGGL(ppo_loss_fwd_kernel<true>, dim3(nblk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(ppo_loss_fwd_kernel<false>, dim3(nblk), dim3(256), 0, s, a);
-    RLX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ppo_loss_finalize, dim3(1), dim3(256), 0, s, a.partials, nblk, (long long)n_adv, *p,
-                       loss_mask != nullptr ? 1 : 0, loss_mask_sum != nullptr ? 1 : 0, out);
-    RLX_LAUNCH_CHECK();
-    return RLX_OK;
+    LossArgs a{};
+    a.lp = logprobs, a.old = old_logprobs, a.adv = advantages, a.v = values, a.pv = prev_values, a.ret = returns;
+    a.m = loss_mask, a.msum = loss_mask_sum, a.g_lp = g_logp, a.g_v = g_value, a.n = n_adv, a.p.ppo = *p;
+    return loss_fwd("rlx_ppo_loss_fwd", false, a, out, workspace, workspace_bytes, stream);
+}
+
+// Decoupled (asynchronous) PPO, compute_decoupled_ppo_actor[_critic]_loss rlinf/algorithms/losses.py:27-167,383-393 (inputs:
+// rlinf/algorithms/utils.py:310-352; the element math and what "proximal" means: ppo_loss_math.h).  The classic kernels with one
+// more reduction slot, and the same backward (rlx_ppo_loss_bwd).
+extern "C" int rlx_decoupled_loss_fwd(const float* logprobs, const float* old_logprobs, const float* proximal_logprobs,
+                                      const float* versions, const float* advantages, const float* values,
+                                      const float* prev_values, const float* returns, const uint8_t* loss_mask,
+                                      const int64_t* loss_mask_sum, int64_t n_adv, const rlx_decoupled_loss_params* dp,
+                                      float* g_logp, float* g_value, float* out, void* workspace, size_t workspace_bytes,
+                                      rlx_stream_t stream) {
+    RLX_REQUIRE(dp != nullptr && out != nullptr, "rlx_decoupled_loss_fwd: NULL params/out");
+    RLX_REQUIRE(dp->proximal_mode >= RLX_PROX_GIVEN && dp->proximal_mode <= RLX_PROX_FROM_VERSIONS,
+                "rlx_decoupled_loss_fwd: unknown proximal_mode %d", dp->proximal_mode);
+    RLX_REQUIRE(dp->proximal_mode != RLX_PROX_GIVEN || n_adv == 0 || proximal_logprobs,
+                "rlx_decoupled_loss_fwd: proximal_mode GIVEN without proximal_logprobs");
+    RLX_REQUIRE(dp->proximal_mode != RLX_PROX_FROM_VERSIONS || n_adv == 0 || versions,
+                "rlx_decoupled_loss_fwd: proximal_mode FROM_VERSIONS without versions");
+    LossArgs a{};
+    a.lp = logprobs, a.old = old_logprobs, a.prox = proximal_logprobs, a.versions = versions, a.adv = advantages;
+    a.v = values, a.pv = prev_values, a.ret = returns, a.m = loss_mask, a.msum = loss_mask_sum;
+    a.g_lp = g_logp, a.g_v = g_value, a.n = n_adv, a.p = *dp;
+    return loss_fwd("rlx_decoupled_loss_fwd", true, a, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rlx_ppo_loss_bwd(const float* g_logp, const float* g_value, const float* out, const float* grad_out,
@@ -211,7 +252,7 @@ extern "C" int rlx_ppo_loss_bwd(const float* g_logp, const float* g_value, const
     RLX_REQUIRE(g_logp && out && d_logprobs, "rlx_ppo_loss_bwd: NULL argument");
     RLX_REQUIRE(d_values == nullptr || g_value != nullptr, "rlx_ppo_loss_bwd: d_values requested without g_value");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(ppo_loss_bwd_kernel, dim3(loss_grid(n_adv * raw_per_adv)), dim3(256), 0, s, g_logp, g_value, out,
+    hipLaunchKernelGGL(ppo_loss_bwd_kernel, dim3(stream_grid(n_adv * raw_per_adv)), dim3(256), 0, s, g_logp, g_value, out,
                        grad_out, d_logprobs, d_values, (long long)n_adv, raw_per_adv, sub_per_adv);
     RLX_LAUNCH_CHECK();
     return RLX_OK;

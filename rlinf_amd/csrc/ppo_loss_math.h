@@ -75,9 +75,10 @@ __device__ __forceinline__ float actor_elem(const rlx_ppo_loss_params& p, float 
     return g;
 }
 
-// One element of the critic: returns d(sum-form value loss)/d(v).
+// One element of the critic: returns d(sum-form value loss)/d(v).  (N: the decoupled rows are one slot longer.)
+template <int N>
 __device__ __forceinline__ float critic_elem(const rlx_ppo_loss_params& p, float v, float pv, float ret, bool on, float w,
-                                             bool ratio_mode, float half_delta, double (&acc)[NS]) {
+                                             bool ratio_mode, float half_delta, double (&acc)[N]) {
     const float mf = on ? 1.f : 0.f;
     const float diff = fsub(v, pv);
     const float cl = fminf(fmaxf(diff, -p.value_clip), p.value_clip);

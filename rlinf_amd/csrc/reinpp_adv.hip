@@ -369,23 +369,12 @@ constexpr int MAX_GROUPS = 64;
 
 __global__ __launch_bounds__(RT) void reinpp_reduce_kernel(const double* __restrict__ partials, long long B,
                                                            double* __restrict__ groups) {
-    __shared__ double s_red[3][RT / RLX_WAVE];
+    __shared__ double s_red[3 * (RT / RLX_WAVE)];
     double acc[3] = {0.0, 0.0, 0.0};
     for (long long b = (long long)blockIdx.x * RT + threadIdx.x; b < B; b += (long long)gridDim.x * RT) {
         acc[0] += partials[b * 3], acc[1] += partials[b * 3 + 1], acc[2] += partials[b * 3 + 2];
     }
-    const int lane = threadIdx.x & (RLX_WAVE - 1), wave = threadIdx.x / RLX_WAVE;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        acc[k] = wave_sum(acc[k]);
-        if (lane == 0) s_red[k][wave] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double t = 0.0;
-        for (int w = 0; w < RT / RLX_WAVE; ++w) t += s_red[threadIdx.x][w];
-        groups[blockIdx.x * 3 + threadIdx.x] = t;
-    }
+    store_partials<3>(acc, s_red, groups);
 }
 
 // every workgroup folds the (at most 64) group sums itself, in the same order -- no third launch, identical statistics
@@ -439,10 +428,7 @@ extern "C" int rlx_reinpp_seq_adv(const float* rewards, const uint8_t* loss_mask
     RLX_REQUIRE(rewards && loss_mask && advantages && workspace, "rlx_reinpp_seq_adv: NULL argument");
     RLX_REQUIRE(!(kl_beta > 0.f) || (logprob && ref_logprob && kl_type >= RLX_KL_K1 && kl_type <= RLX_KL_K3),
                 "rlx_reinpp_seq_adv: kl_beta > 0 needs logprob, ref_logprob and a kl type (got %d)", kl_type);
-    if (workspace_bytes < rlx_reinpp_workspace_bytes(bsz)) {
-        set_error("rlx_reinpp_seq_adv: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_reinpp_workspace_bytes(bsz), "rlx_reinpp_seq_adv");
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* partials = static_cast<double*>(workspace);
     double* groups = partials + (size_t)bsz * 3;

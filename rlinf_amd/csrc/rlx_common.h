@@ -53,22 +53,6 @@ __device__ __forceinline__ float fmul(float a, float b) { return __fmul_rn(a, b)
 __device__ __forceinline__ float fadd(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float fsub(float a, float b) { return __fsub_rn(a, b); }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, RLX_WAVE);
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, RLX_WAVE);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, RLX_WAVE);
-    return v;
-}
-
 // Touch every 64-byte line of the first BYTES of the kernel-argument block at kernel start (scalar loads, all in flight together).
 // A kernel whose argument structs span many lines otherwise pays one scalar-cache miss -- a trip to memory, microseconds when the
 // chip is busy -- at every FIRST use of a new line, serially, wherever in the kernel that use happens to be.
@@ -82,30 +66,8 @@ __device__ __forceinline__ void touch_kernargs() {
     asm volatile("" ::"s"(touch));
 }
 
-// Block-wide sum of K doubles per thread.  `scratch` must hold K * (blockDim.x/64) doubles.
-// Result valid in thread 0 only.  Deterministic (fixed tree).
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* scratch) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    if (nw == 1) return;
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) scratch[wid * K + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = 0.0;
-            for (int w = 0; w < nw; ++w) s += scratch[w * K + k];
-            v[k] = s;
-        }
-    }
-}
-
 #endif  // __HIPCC__
 
 }  // namespace rlx
+
+#include "rlx_reduce.h"  // wave_sum, block_sum and the two-stage reduction built on them

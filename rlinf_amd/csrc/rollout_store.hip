@@ -125,9 +125,8 @@ __global__ __launch_bounds__(128) void version_stats_final_kernel(const long lon
 }
 
 int vs_blocks(long long n) {
-    const long long per_block = (long long)VS_THREADS * 16;  // >= 16 elements (four 16-byte loads) per thread before a second block pays
-    return (int)std::max<long long>(1, std::min<long long>({(n + per_block - 1) / per_block, (long long)VS_MAX_BLOCKS,
-                                                            (long long)num_cu() * 4}));
+    // >= 16 elements (four 16-byte loads) per thread before a second block pays
+    return stream_grid(n, VS_THREADS * 16, VS_MAX_BLOCKS);
 }
 
 // ---- segmented gather --------------------------------------------------------------------------------------------------------

@@ -893,10 +893,7 @@ extern "C" int rlx_token_loss_fwd(const float* logprobs, const float* old_logpro
                 "rlx_token_loss_fwd: clip_ratio_c must be greater than 1.0");
     RLX_REQUIRE(!(params->use_entropy && entropy && params->entropy_bonus != 0.f) || g_entropy,
                 "rlx_token_loss_fwd: entropy_bonus needs g_entropy");
-    if (workspace_bytes < rlx_token_loss_workspace_bytes(bsz, seq)) {
-        set_error("rlx_token_loss_fwd: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_token_loss_workspace_bytes(bsz, seq), "rlx_token_loss_fwd");
     TokLossArgs a;
     a.logprobs = logprobs, a.old_logprobs = old_logprobs, a.advantages = advantages, a.ref_logprobs = ref_logprobs;
     a.entropy = entropy, a.loss_mask = loss_mask, a.bsz = bsz, a.seq = seq, a.p = *params;

@@ -515,10 +515,7 @@ extern "C" int rlx_patch_scan(const void* value, int value_dtype, const void* sn
                               void* workspace, size_t workspace_bytes, int64_t* nnz, rlx_stream_t stream) {
     RLX_REQUIRE(n_elems >= 1 && value && snapshot && workspace && nnz, "rlx_patch_scan: bad argument");
     RLX_REQUIRE(n_elems < (1ll << 45), "rlx_patch_scan: tensor too large");
-    if (workspace_bytes < rlx_patch_workspace_bytes(n_elems)) {
-        set_error("rlx_patch_scan: workspace too small");
-        return RLX_ENOSPC;
-    }
+    RLX_REQUIRE_SPACE(workspace_bytes, rlx_patch_workspace_bytes(n_elems), "rlx_patch_scan");
     const Scratch s = carve(workspace, n_elems);
     const int src = value_dtype, dst = snapshot_dtype;
     hipStream_t st = static_cast<hipStream_t>(stream);
