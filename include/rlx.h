@@ -309,8 +309,11 @@ int rlx_gather_rows_segmented(const rlx_seg_field* fields, int n_fields, int n_s
  * a23  clip_adamw_step  <- FSDPModelManager.optimizer_step, rlinf/hybrid_engines/fsdp/fsdp_model_manager.py:429-463
  *        = torch.nn.utils.clip_grad_norm_ (strategy/fsdp.py:363-369) + torch.optim.AdamW.step
  *          with the two parameter groups of build_optimizer (fsdp_model_manager.py:501-590)
- * Flat f32 buffers of n elements: params, grads, exp_avg, exp_avg_sq.  `groups` partitions [0, n)
- * into ranges with their own learning rate (names containing "value_head" use value_lr).
+ * Flat f32 buffers of n elements: params, grads, exp_avg, exp_avg_sq.  `groups` covers [0, n) or part
+ * of it with disjoint ranges that have their own learning rate (names containing "value_head" use value_lr).  Non-empty ranges
+ * that overlap are refused (RLX_EINVAL); ranges may leave gaps, be empty, and begin or end anywhere (also inside a float4): an
+ * element of no range keeps its parameter and moments bit for bit while its gradient is still clipped; n_groups == 0 clips the
+ * gradient and writes stats only.
  *   total_norm = ||grads||_2;  grads *= min(1, max_norm / (total_norm + 1e-6))  (always applied)
  *   if total_norm is non-finite the AdamW update is skipped (step count is the caller's to keep)
  *   p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2*v + (1-b2)*g*g;

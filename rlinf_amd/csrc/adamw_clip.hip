@@ -327,10 +327,13 @@ __device__ __forceinline__ void update_values_f4(float* __restrict__ p, float* _
     pe[0] = p4.x, pe[1] = p4.y, pe[2] = p4.z, pe[3] = p4.w;
     grp[0] = grp[1] = grp[2] = grp[3] = -1;
     if (live) {
+        // both ends in ONE group: so is the middle (a group is one range).  Both ends in NO group says nothing about the middle --
+        // a one- or two-element group may lie strictly inside the float4 -- so it is looked up, like in the scalar form.
         const int g_first = group_of(a, 4 * i), g_last = group_of(a, 4 * i + 3);
+        const bool same = g_first == g_last && g_first >= 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            grp[e] = (e == 0) ? g_first : (e == 3 ? g_last : (g_first == g_last ? g_first : group_of(a, 4 * i + e)));
+            grp[e] = (e == 0) ? g_first : (e == 3 ? g_last : (same ? g_first : group_of(a, 4 * i + e)));
             adamw_elem(pe[e], ge[e], me[e], ve[e], coef, grp[e], skip, sc);
         }
         reinterpret_cast<float4*>(g)[i] = float4{ge[0], ge[1], ge[2], ge[3]};
@@ -1159,6 +1162,12 @@ int check_adamw_args(float* params, float* out, float* exp_avg, float* exp_avg_s
     for (int k = 0; k < p->n_groups; ++k)
         RLX_REQUIRE(p->groups[k].begin >= 0 && p->groups[k].end <= n && p->groups[k].begin <= p->groups[k].end,
                     "rlx_clip_adamw_step: group %d range out of bounds", k);
+    // disjoint: the float4 forms take "first and last element in one group" to decide the two between them
+    for (int k = 0; k < p->n_groups; ++k)
+        for (int j = 0; j < k; ++j)
+            RLX_REQUIRE(p->groups[k].begin >= p->groups[k].end || p->groups[j].begin >= p->groups[j].end ||
+                            p->groups[k].begin >= p->groups[j].end || p->groups[j].begin >= p->groups[k].end,
+                        "rlx_clip_adamw_step: groups %d and %d overlap", j, k);
     tiles = nullptr;
     if (p->tile_layout != nullptr && p->tiles != nullptr) {
         lay = *p->tile_layout;

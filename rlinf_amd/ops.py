@@ -822,13 +822,15 @@ def clip_adamw_step_(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.T
     for t in (params, grads, exp_avg, exp_avg_sq):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise RlxError("clip_adamw_step_ needs contiguous float32 buffers")
-    if grads.numel() % max(n, 1) != 0 or exp_avg.numel() != n or exp_avg_sq.numel() != n:
+    if grads.numel() % max(n, 1) != 0 or grads.numel() < n or exp_avg.numel() != n or exp_avg_sq.numel() != n:
         raise RlxError("buffer sizes do not match")
-    p = _adamw_params(groups, grads.numel() // max(n, 1), step, betas=betas, eps=eps, weight_decay=weight_decay,
-                      max_grad_norm=max_grad_norm, grad_scale=grad_scale, tile_layout=tile_layout, tiles=tiles, deferred=deferred,
-                      sync=sync)
     if stats is None:
         stats = torch.empty((2,), dtype=torch.float32, device=dev)
+    if n == 0:  # nothing to update and nothing to launch (the library returns before it writes stats, too)
+        return stats
+    p = _adamw_params(groups, grads.numel() // n, step, betas=betas, eps=eps, weight_decay=weight_decay,
+                      max_grad_norm=max_grad_norm, grad_scale=grad_scale, tile_layout=tile_layout, tiles=tiles, deferred=deferred,
+                      sync=sync)
     ws_bytes = lib.rlx_adamw_workspace_bytes(n)
     ws = workspace if workspace is not None and workspace.numel() >= ws_bytes else _lib.workspace(dev, ws_bytes)
     if step_state is not None and (step_state.dtype != torch.int32 or step_state.numel() < 2):
