@@ -1,5 +1,6 @@
 /*
- * rlx.h -- C ABI of the MI355X-native rollout + PPO/GRPO update hot path (librlx_hip.so).
+ * rlx.h -- C ABI of the MI355X-native rollout + PPO/GRPO update hot path and of the SAC (Q-head) MLP policy's model
+ *          calls (librlx_hip.so).
  *
  * The reference (RLinf, /root/reference) has NO native/FFI layer: its extension surface is the
  * Python registries in rlinf/algorithms/registry.py:30-124 and rlinf/models/__init__.py:31-53.
@@ -32,8 +33,8 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 117 /* 0.1.7: bumped whenever an argument struct or a signature changes (0.1.7: the rollout-store entries
-                           * rlx_version_stats, rlx_gather_rows_segmented, rlx_abi_struct_sizes_ext; 0.1.6: rlx_grpo_video_adv,
+#define RLX_VERSION 118 /* 0.1.8: bumped whenever an argument struct or a signature changes (0.1.8: the SAC entries rlx_sac_*;
+                           * 0.1.7: the rollout-store entries rlx_version_stats, rlx_gather_rows_segmented, rlx_abi_struct_sizes_ext; 0.1.6: rlx_grpo_video_adv,
                            * rlx_raw_adv, rlx_raw_adv_workspace_bytes; 0.1.5: the development-build query removed;
                            * 0.1.4: rlx_grpo_dynamic_adv, rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries
                            * rlx_opd_*; round 6: rlx_xgmi_self_timing, the
@@ -58,8 +59,9 @@ const char* rlx_last_error(void);
  * token_rows, token_loss_params, copy_segment): a binding written in another language checks its mirrors against these at
  * load time instead of discovering a stale layout through a wrong result.  Writes min(n, 13) entries, returns 13. */
 int rlx_abi_struct_sizes(size_t* sizes, int n);
-/* The same for the structs that came after those 13, in declaration order (version_stats_out, seg_field).  The first list is frozen:
- * bindings check its length, so structs added later are reported here.  Writes min(n, 2) entries, returns 2. */
+/* The same for the structs that came after those 13, in declaration order (version_stats_out, seg_field, sac_actor_layout,
+ * sac_q_layout).  The first list is frozen: bindings check its length, so structs added later are reported here.  Writes
+ * min(n, 4) entries, returns 4. */
 int rlx_abi_struct_sizes_ext(size_t* sizes, int n);
 
 /* Number of compute units / wave size of the current device (plumbing for launch heuristics). */
@@ -1047,6 +1049,74 @@ int rlx_opd_loss_fwd(const float* logprobs, const float* advantages, const uint8
 int rlx_opd_loss_bwd(const float* advantages, const uint8_t* loss_mask, int mask_div, const void* loss_mask_sum, int msum_div,
                      int msum_i64, int64_t n, int max_episode_steps, const float* out, const float* grad_out,
                      float* d_logprobs, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SAC (Q-head) variant of the MLP policy  <- MLPPolicy(add_q_head=True, q_head_type="default"),
+ *     rlinf/models/embodiment/mlp_policy/mlp_policy.py:179-200 (sac_forward), :238-293, :322-323 (sac_q_forward);
+ *     MultiQHead / QHead rlinf/models/embodiment/modules/q_head.py:22-160; make_mlp modules/utils.py:38-50;
+ *     Normal.rsample / log_prob and autograd's backward through all of it.
+ * f32 only; hidden == 256; 1 <= obs_dim <= 64; 1 <= act_dim <= 16.  The actor and the Q ensemble each read ONE flat f32
+ * buffer of their own whose element offsets the layout structs hold (weights row-major [out, in]; offsets of the 256-wide
+ * weights are multiples of 4).  Dense 256-wide layers run on the exact-f32 MFMA; one workgroup owns a 32-row tile.
+ *   actor: backbone.{0,2,4} (tanh), then ONE [2*act_dim, 256] head: rows [0, act_dim) = actor_mean, the rest = actor_logstd
+ *   Q:     head h of 2: net.{0,3,6} Linear, net.{1,4,7} LayerNorm(256, eps 1e-5, biased variance), tanh, net.9 Linear(256, out)
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rlx_sac_actor_layout {
+    int32_t obs_dim;     /* D */
+    int32_t act_dim;     /* A' = num_action_chunks * action_dim */
+    int32_t hidden;      /* must be 256 */
+    int32_t reserved;
+    int64_t n_params;    /* elements of the actor's flat buffer */
+    int64_t off_w[3];    /* backbone weights */
+    int64_t off_b[3];    /* backbone biases */
+    int64_t off_wh;      /* head weight [2A', 256]: actor_mean.weight then actor_logstd.weight */
+    int64_t off_bh;      /* head bias [2A'] */
+    float logstd_lo;     /* logstd = lo + 0.5 (hi - lo) (tanh(raw) + 1); the reference's range is (-5, 2) */
+    float logstd_hi;
+} rlx_sac_actor_layout;
+
+typedef struct rlx_sac_q_layout {
+    int32_t obs_dim;        /* D (the critic's observation width) */
+    int32_t act_dim;        /* A' */
+    int32_t out_dim;        /* Q values per head: 1 (chunk_level) or num_action_chunks */
+    int32_t hidden;         /* must be 256 */
+    int64_t n_params;       /* elements of the Q ensemble's flat buffer */
+    int64_t off_w[2][4];    /* [head][layer] Linear weight; layer 0 is [256, D + A'] over cat(states, actions) */
+    int64_t off_b[2][4];    /* [head][layer] Linear bias */
+    int64_t off_g[2][3];    /* [head][layer] LayerNorm weight */
+    int64_t off_beta[2][3]; /* [head][layer] LayerNorm bias */
+} rlx_sac_q_layout;
+
+/* Actor forward (one launch): states [M, D], eps [M, A'] N(0,1) draws or NULL (raw = mean: eval) ->
+ *   action = tanh(mean + exp(logstd) eps) * action_scale + action_bias,
+ *   logprob = Normal(mean, std).log_prob(raw) - log(action_scale (1 - tanh(raw)^2) + 1e-6), both [M, A'].
+ * Training form: acts [3][M][256] (hidden activations) and aux [2][M][A'] (tanh of the raw log-std, tanh(raw)) are kept for
+ * backward.  No-grad form: acts == aux == NULL, nothing is kept. */
+int rlx_sac_actor_fwd(const float* params, const rlx_sac_actor_layout* layout, const float* states, const float* eps, int64_t m,
+                      float action_scale, float action_bias, float* action, float* logprob, float* acts, float* aux,
+                      rlx_stream_t stream);
+/* Actor backward through the rsample, the tanh squash and the log term: d_action, d_logprob [M, A'] (either may be NULL = zero)
+ * -> grads [slabs][n_params] split-K slabs, every element written (rlx_sum_slabs reduces them).
+ *   workspace: rlx_sac_actor_bwd_workspace_bytes(layout, m) bytes; slabs: rlx_sac_actor_bwd_slabs(m). */
+int rlx_sac_actor_bwd_slabs(int64_t m);
+size_t rlx_sac_actor_bwd_workspace_bytes(const rlx_sac_actor_layout* layout, int64_t m);
+int rlx_sac_actor_bwd(const float* params, const rlx_sac_actor_layout* layout, const float* states, const float* eps,
+                      const float* acts, const float* aux, const float* d_action, const float* d_logprob, int64_t m,
+                      float action_scale, float* grads, int slabs, void* workspace, size_t workspace_bytes, rlx_stream_t stream);
+
+/* Q ensemble forward (one launch): q [M, 2 * out_dim], head h in columns [h * out_dim, (h + 1) * out_dim); the first layer reads
+ * states [M, D] and actions [M, A'] side by side (no concatenated copy).  Training form keeps acts [2][3][2][M][256]
+ * ([head][layer][0 = tanh output, 1 = normalised pre-activation]) and rstd [2][3][M]; no-grad form: both NULL. */
+int rlx_sac_q_fwd(const float* params, const rlx_sac_q_layout* layout, const float* states, const float* actions, int64_t m,
+                  float* q, float* acts, float* rstd, rlx_stream_t stream);
+/* Q ensemble backward from d_q [M, 2 * out_dim].  Each output is optional (NULL = not wanted):
+ *   grads [slabs][n_params] split-K slabs of every Q parameter, every element written;
+ *   d_actions [M, A'] (the actor loss back-propagates through Q into the action).  No gradient with respect to states. */
+int rlx_sac_q_bwd_slabs(int64_t m);
+size_t rlx_sac_q_bwd_workspace_bytes(const rlx_sac_q_layout* layout, int64_t m);
+int rlx_sac_q_bwd(const float* params, const rlx_sac_q_layout* layout, const float* states, const float* actions,
+                  const float* acts, const float* rstd, const float* d_q, int64_t m, float* grads, int slabs, float* d_actions,
+                  void* workspace, size_t workspace_bytes, rlx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,18 @@ class MlpLayout(Structure):
     ]
 
 
+class SacActorLayout(Structure):  # include/rlx.h: rlx_sac_actor_layout
+    _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("hidden", c_int32), ("reserved", c_int32), ("n_params", c_int64),
+                ("off_w", c_int64 * 3), ("off_b", c_int64 * 3), ("off_wh", c_int64), ("off_bh", c_int64),
+                ("logstd_lo", c_float), ("logstd_hi", c_float)]
+
+
+class SacQLayout(Structure):  # include/rlx.h: rlx_sac_q_layout
+    _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("out_dim", c_int32), ("hidden", c_int32), ("n_params", c_int64),
+                ("off_w", (c_int64 * 4) * 2), ("off_b", (c_int64 * 4) * 2), ("off_g", (c_int64 * 3) * 2),
+                ("off_beta", (c_int64 * 3) * 2)]
+
+
 class AdamwParams(Structure):
     _fields_ = [
         ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
@@ -292,6 +304,17 @@ PROTOTYPES = {
     "rlx_xgmi_allreduce_f32": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float, c_void_p, c_size_t, c_void_p]),
     "rlx_xgmi_clip_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                          POINTER(AdamwParams), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rlx_sac_actor_fwd": (c_int, [c_void_p, POINTER(SacActorLayout), c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_sac_actor_bwd_slabs": (c_int, [c_int64]),
+    "rlx_sac_actor_bwd_workspace_bytes": (c_size_t, [POINTER(SacActorLayout), c_int64]),
+    "rlx_sac_actor_bwd": (c_int, [c_void_p, POINTER(SacActorLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rlx_sac_q_fwd": (c_int, [c_void_p, POINTER(SacQLayout), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_sac_q_bwd_slabs": (c_int, [c_int64]),
+    "rlx_sac_q_bwd_workspace_bytes": (c_size_t, [POINTER(SacQLayout), c_int64]),
+    "rlx_sac_q_bwd": (c_int, [c_void_p, POINTER(SacQLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 XGMI_HANDLE_BYTES, XGMI_MAX_RANKS = 64, 8
 
@@ -318,11 +341,11 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 117:
+    if lib.rlx_version() < 118:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents
-    later = (VersionStats, SegField)  # the order rlx_abi_struct_sizes_ext documents
+    later = (VersionStats, SegField, SacActorLayout, SacQLayout)  # the order rlx_abi_struct_sizes_ext documents
     for query, classes, which in ((lib.rlx_abi_struct_sizes, mirrors, ""), (lib.rlx_abi_struct_sizes_ext, later, "later ")):
         sizes = (c_size_t * len(classes))()
         if query(ctypes.cast(sizes, c_void_p), len(classes)) != len(classes):

@@ -203,13 +203,22 @@ class ReferenceNamedMLPPolicy(nn.Module):
 
 def build_reference_named_mlp_policy(cfg, torch_dtype):
     """``ModelBuilder(cfg, torch_dtype) -> nn.Module`` for rlinf.models.register_model; reads the keys the reference's own
-    builder reads (rlinf/models/embodiment/mlp_policy/__init__.py:19-75).  The Q-head (SAC / CrossQ) and IQL variants are not
-    on the PPO / GRPO path this package replaces: for those the reference's own builder is called, unchanged."""
+    builder reads (rlinf/models/embodiment/mlp_policy/__init__.py:19-75).  SAC configurations (``add_q_head`` with the default Q
+    head) get the HIP SAC module (sac_mlp_policy.py).  The CrossQ (BatchRenorm) and IQL variants are not served here: for those
+    the reference's own builder is called, unchanged."""
     get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
-    if get("add_q_head", False) or get("iql_config", None) is not None:
+    if get("iql_config", None) is not None or (get("add_q_head", False) and get("q_head_type", "default") != "default"):
         from rlinf.models.embodiment.mlp_policy import get_model as reference_builder
 
         return reference_builder(cfg, torch_dtype)
+    if get("add_q_head", False):
+        from .sac_mlp_policy import SacMLPPolicy
+
+        return SacMLPPolicy(
+            obs_dim=int(get("obs_dim")), action_dim=int(get("action_dim")), num_action_chunks=int(get("num_action_chunks", 1)),
+            add_value_head=bool(get("add_value_head", False)), add_q_head=True, q_head_type="default",
+            value_granularity=get("value_granularity", "action_level"), critic_obs_dim=get("critic_obs_dim", None),
+            compute_dtype=torch.bfloat16 if torch_dtype == torch.bfloat16 else torch.float32)
     return ReferenceNamedMLPPolicy(
         obs_dim=int(get("obs_dim")), action_dim=int(get("action_dim")), num_action_chunks=int(get("num_action_chunks", 1)),
         add_value_head=bool(get("add_value_head", True)), add_q_head=False, q_head_type=get("q_head_type", "default"),

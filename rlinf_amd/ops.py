@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import (AdamwGroup, AdamwParams, GaeParams, GatherField, MlpLayout, PpoLossParams, PpoStepArgs, RlxError,
-                   RolloutStep)
+                   RolloutStep, SacActorLayout, SacQLayout)
 
 
 def _dev(*tensors) -> torch.device:
@@ -972,6 +972,70 @@ def mlp_train_bwd(params, packed, layout: MlpLayout, states, action, mean, acts,
     _lib.launch("rlx_mlp_train_bwd", dev, params, packed, layout, states, action, mean, acts, dl, de, dv, M, grads, slabs, workspace,
                 workspace.numel())
     return grads
+
+
+# --------------------------------------------------------------------------------------------
+# SAC (Q-head) MLP policy: the model calls (sac_mlp.hip)
+# --------------------------------------------------------------------------------------------
+def sac_actor_fwd(params, layout: SacActorLayout, states, eps: Optional[torch.Tensor], action_scale: float, action_bias: float,
+                  train: bool):
+    """-> (action, logprob [M, A'], acts [3,M,256] | None, aux [2,M,A'] | None); ``train`` keeps what backward needs."""
+    dev = _dev(params, states, eps)
+    st, ep = _as_f32(states, "states"), _as_f32(eps, "eps")
+    M, A = st.shape[0], layout.act_dim
+    if st.dim() != 2 or st.shape[1] != layout.obs_dim:
+        raise RlxError(f"states must be [M, {layout.obs_dim}], got {tuple(st.shape)}")
+    if ep is not None and tuple(ep.shape) != (M, A):
+        raise RlxError(f"eps must be [{M}, {A}], got {tuple(ep.shape)}")
+    action = torch.empty((M, A), dtype=torch.float32, device=dev)
+    logprob = torch.empty_like(action)
+    acts = torch.empty((3, M, 256), dtype=torch.float32, device=dev) if train else None
+    aux = torch.empty((2, M, A), dtype=torch.float32, device=dev) if train else None
+    _lib.launch("rlx_sac_actor_fwd", dev, params, layout, st, ep, M, action_scale, action_bias, action, logprob, acts, aux)
+    return action, logprob, acts, aux
+
+
+def sac_actor_bwd(params, layout: SacActorLayout, states, eps, acts, aux, d_action, d_logprob, action_scale: float):
+    """-> grads [slabs, n_params] (split-K slabs; every element written)."""
+    lib = _lib.load()
+    dev = _dev(params, states, eps, acts, aux, d_action, d_logprob)
+    M = states.shape[0]
+    slabs = lib.rlx_sac_actor_bwd_slabs(M)
+    grads = torch.empty((slabs, layout.n_params), dtype=torch.float32, device=dev)
+    workspace = _lib.workspace(dev, lib.rlx_sac_actor_bwd_workspace_bytes(byref(layout), M))
+    _lib.launch("rlx_sac_actor_bwd", dev, params, layout, states, eps, acts, aux, _as_f32(d_action, "d_action"),
+                _as_f32(d_logprob, "d_logprob"), M, action_scale, grads, slabs, workspace, workspace.numel())
+    return grads
+
+
+def sac_q_fwd(params, layout: SacQLayout, states, actions, train: bool):
+    """-> (q [M, 2*out], acts [2,3,2,M,256] | None, rstd [2,3,M] | None)."""
+    dev = _dev(params, states, actions)
+    st, ac = _as_f32(states, "states"), _as_f32(actions, "actions")
+    M = st.shape[0]
+    if st.dim() != 2 or st.shape[1] != layout.obs_dim:
+        raise RlxError(f"states must be [M, {layout.obs_dim}], got {tuple(st.shape)}")
+    if tuple(ac.shape) != (M, layout.act_dim):
+        raise RlxError(f"actions must be [{M}, {layout.act_dim}], got {tuple(ac.shape)}")
+    q = torch.empty((M, 2 * layout.out_dim), dtype=torch.float32, device=dev)
+    acts = torch.empty((2, 3, 2, M, 256), dtype=torch.float32, device=dev) if train else None
+    rstd = torch.empty((2, 3, M), dtype=torch.float32, device=dev) if train else None
+    _lib.launch("rlx_sac_q_fwd", dev, params, layout, st, ac, M, q, acts, rstd)
+    return q, acts, rstd
+
+
+def sac_q_bwd(params, layout: SacQLayout, states, actions, acts, rstd, d_q, want_params: bool, want_actions: bool):
+    """-> (grads [slabs, n_params] | None, d_actions [M, A'] | None): only what is asked for is computed."""
+    lib = _lib.load()
+    dev = _dev(params, states, actions, acts, rstd, d_q)
+    M = states.shape[0]
+    slabs = lib.rlx_sac_q_bwd_slabs(M)
+    grads = torch.empty((slabs, layout.n_params), dtype=torch.float32, device=dev) if want_params else None
+    d_actions = torch.empty((M, layout.act_dim), dtype=torch.float32, device=dev) if want_actions else None
+    workspace = _lib.workspace(dev, lib.rlx_sac_q_bwd_workspace_bytes(byref(layout), M))
+    _lib.launch("rlx_sac_q_bwd", dev, params, layout, states, actions, acts, rstd, _as_f32(d_q, "d_q"), M, grads, slabs, d_actions,
+                workspace, workspace.numel())
+    return grads, d_actions
 
 
 # --------------------------------------------------------------------------------------------
