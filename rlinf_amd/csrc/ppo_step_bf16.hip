@@ -145,7 +145,7 @@ __device__ __forceinline__ void store_tiles(const bf16x4 (*v)[GeoB<RT, NW>::CT],
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const int cb = wave * CT + ct;
-            *reinterpret_cast<bf16x4*>(dst + ((size_t)(cb * nrb + rb) * 64 + kblk * 16 + r16) * 8 + 4 * (kq & 1)) = v[rt][ct];
+            wt::store(reinterpret_cast<bf16x4*>(dst + ((size_t)(cb * nrb + rb) * 64 + kblk * 16 + r16) * 8 + 4 * (kq & 1)), v[rt][ct]);
         }
     }
 }
@@ -218,6 +218,7 @@ struct StatesB {
     // after an LDS barrier behind commit()
     __device__ __forceinline__ static void tiles(__bf16* __restrict__ st_tiles, int nrb, int D, long long m0, const __bf16* Xb) {
         const int kp = round_up(D, KPAD);
+        const wt::Span sp = wt::span(st_tiles, (size_t)4 * nrb * 512 * sizeof(__bf16));  // 4 column blocks x nrb row blocks x 1 KiB
         for (int u = threadIdx.x; u < 4 * (G::BM / 8) * 16; u += G::NT) {
             const int cb = u / ((G::BM / 8) * 16), ko = (u / 16) % (G::BM / 8), c16 = u & 15;
             const int rb = (int)(m0 >> 5) + (ko >> 2);
@@ -225,7 +226,7 @@ struct StatesB {
             bf16x8 v;
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = cb * 16 + c16 < kp ? Xb[(8 * ko + j) * XSB + cb * 16 + c16] : (__bf16)0.f;
-            *reinterpret_cast<bf16x8*>(st_tiles + ((size_t)(cb * nrb + rb) * 64 + (ko & 3) * 16 + c16) * 8) = v;
+            wt::store16(sp, ((size_t)(cb * nrb + rb) * 64 + (ko & 3) * 16 + c16) * 8 * sizeof(__bf16), v);
         }
     }
 };
@@ -539,7 +540,7 @@ __global__ __launch_bounds__(512, 4) void ppo_step_fused_bf16_kernel(StepArgs a,
                 const int j = wave * 16 * CT + ct * 16 + r16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (4 * kq + r < n_out) part[(4 * kq + r) * HID + j] = g[r];
+                    if (4 * kq + r < n_out) wt::store(part + (4 * kq + r) * HID + j, g[r]);
             }
             if (wave == 0) {  // bias / log-std gradients: row sums, i.e. the same product against a fragment of ones
                 const f32x4 gb = mfma3(A, ones, zero4);
@@ -548,8 +549,8 @@ __global__ __launch_bounds__(512, 4) void ppo_step_fused_bf16_kernel(StepArgs a,
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (4 * kq + r < n_out) {
-                            part[n_out * HID + 4 * kq + r] = gb[r];
-                            part[n_out * HID + n_out + 4 * kq + r] = gl[r];
+                            wt::store(part + n_out * HID + 4 * kq + r, gb[r]);
+                            wt::store(part + n_out * HID + n_out + 4 * kq + r, gl[r]);
                         }
                 }
             }
@@ -742,7 +743,7 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = i0 + wi * 64 + ti * 16 + 4 * kq + r;
-                    dW[(size_t)row * Kin + col] = acc[ti][tj][r];
+                    wt::store(dW + (size_t)row * Kin + col, acc[ti][tj][r]);
                 }
             }
         }
@@ -752,7 +753,7 @@ __global__ __launch_bounds__(256, 2) void ppo_step_dw_bf16_lds_kernel(DwArgs a, 
             float tot = bsum[ti];
             tot += __shfl_xor(tot, 16, 64);
             tot += __shfl_xor(tot, 32, 64);
-            if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
+            if (kq == 0) wt::store(slab + lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16, tot);
         }
     }
 }
@@ -902,6 +903,7 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
         // instruction: 16 lanes write one full 256-byte row of the gradient
         constexpr int SS = 68;
         float* stage = reinterpret_cast<float*>(dsm) + wave * 32 * SS;
+        const wt::Span dw_sp = wt::span(dW, (size_t)HID * HID * sizeof(float));  // this hidden matrix's gradient in slab s
 #pragma unroll
         for (int hp = 0; hp < 2; ++hp) {
 #pragma unroll
@@ -916,7 +918,7 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
             for (int u = 0; u < 8; ++u) {
                 const int idx = lane + 64 * u, row = idx >> 4, c4 = idx & 15;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(stage + row * SS + 4 * c4);
-                *reinterpret_cast<f32x4*>(dW + (size_t)(i0 + wi * 64 + hp * 32 + row) * HID + j0 + wj * 64 + 4 * c4) = v;
+                wt::store16(dw_sp, ((size_t)(i0 + wi * 64 + hp * 32 + row) * HID + j0 + wj * 64 + 4 * c4) * sizeof(float), v);
             }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -931,7 +933,7 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = i0 + wi * 64 + ti * 16 + 4 * kq + r;
-                        dW[(size_t)row * Kin + col] = acc[ti][tj][r];
+                        wt::store(dW + (size_t)row * Kin + col, acc[ti][tj][r]);
                     }
                 }
             }
@@ -942,7 +944,7 @@ __global__ __launch_bounds__(DWR_THREADS) void ppo_step_dw_bf16_ring_kernel(DwAr
             float tot = bsum[ti];
             tot += __shfl_xor(tot, 16, 64);
             tot += __shfl_xor(tot, 32, 64);
-            if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
+            if (kq == 0) wt::store(slab + lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16, tot);
         }
     }
 }

@@ -10,6 +10,7 @@
 #include "ppo_loss_math.h"
 #include "ppo_step_form.h"
 #include "rlx_common.h"
+#include "rlx_store.h"
 
 namespace rlx {
 namespace step {
@@ -280,7 +281,7 @@ __device__ __forceinline__ void head_reduce_block(const DwArgs& a, int s, int y,
         }
 #pragma unroll
         for (int q = 0; q < OB; ++q)
-            if (o0 + q < n_out) slab[lay.off_w[y][3] + (size_t)(o0 + q) * HID + j] = acc[q];
+            if (o0 + q < n_out) wt::store(slab + lay.off_w[y][3] + (size_t)(o0 + q) * HID + j, acc[q]);
     }
     if (j < n_out) {
         float sb = 0.f, sl = 0.f;
@@ -299,8 +300,8 @@ __device__ __forceinline__ void head_reduce_block(const DwArgs& a, int s, int y,
                     sl += xl[u];
                 }
         }
-        if (lay.off_b[y][3] >= 0) slab[lay.off_b[y][3] + j] = sb;
-        if (y == 1) slab[lay.off_logstd + j] = sl;
+        if (lay.off_b[y][3] >= 0) wt::store(slab + lay.off_b[y][3] + j, sb);
+        if (y == 1) wt::store(slab + lay.off_logstd + j, sl);
     }
 }
 #endif

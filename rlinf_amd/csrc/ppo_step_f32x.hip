@@ -172,7 +172,9 @@ struct RowGemmX {
     }
 };
 
-// k-tiled transposed bf16 image (the weight-gradient GEMM's operand layout, see store_tiles in ppo_step_bf16.hip), one plane
+// k-tiled transposed bf16 image (the weight-gradient GEMM's operand layout, see store_tiles in ppo_step_bf16.hip), one plane.
+// Plain stores, unlike the bf16 launch's write-through ones (rlx_store.h): the backward sweep reads these words back in the same
+// launch (load_tiles_x), and write-through stores of this launch's other images measured slower.
 template <int RT, int CT>
 __device__ __forceinline__ void store_tiles_x(const bf16x4 (&v)[RT][CT], __bf16* __restrict__ dst, int nrb, long long m0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r16 = lane & 15, kq = lane >> 4;
@@ -744,6 +746,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
     if (live && l != 0 && vec_ok) {
         constexpr int SS = 68;
         float* stage = reinterpret_cast<float*>(dsm) + wave * 32 * SS;
+        const wt::Span dw_sp = wt::span(dW, (size_t)HID * HID * sizeof(float));  // this hidden matrix's gradient in slab s
 #pragma unroll
         for (int hp = 0; hp < 2; ++hp) {
 #pragma unroll
@@ -758,7 +761,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
             for (int u = 0; u < 8; ++u) {
                 const int idx = lane + 64 * u, row = idx >> 4, c4 = idx & 15;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(stage + row * SS + 4 * c4);
-                *reinterpret_cast<f32x4*>(dW + (size_t)(i0 + wi * 64 + hp * 32 + row) * HID + j0 + wj * 64 + 4 * c4) = v;
+                wt::store16(dw_sp, ((size_t)(i0 + wi * 64 + hp * 32 + row) * HID + j0 + wj * 64 + 4 * c4) * sizeof(float), v);
             }
             asm volatile("" ::: "memory");
             __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -773,7 +776,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = i0 + wi * 64 + ti * 16 + 4 * kq + r;
-                        dW[(size_t)row * Kin + col] = acc[ti][tj][r];
+                        wt::store(dW + (size_t)row * Kin + col, acc[ti][tj][r]);
                     }
                 }
             }
@@ -784,7 +787,7 @@ __global__ __launch_bounds__(DWX_THREADS) void ppo_step_dw_f32x_kernel(DwArgs a,
             float tot = bsum[ti];
             tot += __shfl_xor(tot, 16, 64);
             tot += __shfl_xor(tot, 32, 64);
-            if (kq == 0) slab[lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16] = tot;
+            if (kq == 0) wt::store(slab + lay.off_b[y][l] + i0 + wi * 64 + ti * 16 + r16, tot);
         }
     }
 }
