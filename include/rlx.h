@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define RLX_VERSION 118 /* 0.1.8: bumped whenever an argument struct or a signature changes (0.1.8: the SAC entries rlx_sac_*;
+#define RLX_VERSION 119 /* 0.1.9: bumped whenever an argument struct or a signature changes (0.1.9: the IQL entries rlx_iql_*,
+                           * rlx_soft_update; 0.1.8: the SAC entries rlx_sac_*;
                            * 0.1.7: the rollout-store entries rlx_version_stats, rlx_gather_rows_segmented, rlx_abi_struct_sizes_ext; 0.1.6: rlx_grpo_video_adv,
                            * rlx_raw_adv, rlx_raw_adv_workspace_bytes; 0.1.5: the development-build query removed;
                            * 0.1.4: rlx_grpo_dynamic_adv, rlx_loss_scale_rows, rlx_loss_scale_turn; 0.1.3: the OPD entries
@@ -60,8 +61,8 @@ const char* rlx_last_error(void);
  * load time instead of discovering a stale layout through a wrong result.  Writes min(n, 13) entries, returns 13. */
 int rlx_abi_struct_sizes(size_t* sizes, int n);
 /* The same for the structs that came after those 13, in declaration order (version_stats_out, seg_field, sac_actor_layout,
- * sac_q_layout).  The first list is frozen: bindings check its length, so structs added later are reported here.  Writes
- * min(n, 4) entries, returns 4. */
+ * sac_q_layout, iql_mlp_layout).  The first list is frozen: bindings check its length, so structs added later are reported
+ * here.  Writes min(n, 5) entries, returns 5. */
 int rlx_abi_struct_sizes_ext(size_t* sizes, int n);
 
 /* Number of compute units / wave size of the current device (plumbing for launch heuristics). */
@@ -1117,6 +1118,72 @@ size_t rlx_sac_q_bwd_workspace_bytes(const rlx_sac_q_layout* layout, int64_t m);
 int rlx_sac_q_bwd(const float* params, const rlx_sac_q_layout* layout, const float* states, const float* actions,
                   const float* acts, const float* rstd, const float* d_q, int64_t m, float* grads, int slabs, float* d_actions,
                   void* workspace, size_t workspace_bytes, rlx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Offline IQL for the MLP policy  <- IQLMLPPolicy, rlinf/models/embodiment/mlp_policy/iql_mlp_policy.py:98-117 (_build_mlp),
+ *     :186-210 (iql_forward_actor with actions), :271-283 (critic, value); the loss expressions and the soft update of
+ *     rlinf/workers/actor/fsdp_iql_policy_worker.py:35-38, :408-470, :846-850; autograd's backward through all of it.
+ * f32 only; hidden == 256; 1 <= obs_dim <= 64; 1 <= action_dim <= 32; num_action_chunks == 1.  A network is Linear -> ReLU
+ * repeated n_hidden times, then a Linear head.  n_nets networks of the same shape (the twin critic: q1, q2) share ONE flat
+ * buffer and ONE launch.  Weights are row-major [out, in]; offsets of the 256-wide weights are multiples of 4.
+ *   actor:  in_a = obs_dim, in_b = 0, n_hidden = 3 (backbone.{0,2,4}), head actor_mean 256 -> A, off_logstd = actor_logstd [1, A]
+ *   critic: in_a = obs_dim, in_b = A (the first layer reads obs and actions side by side), n_hidden = 2, head net.4 256 -> 1
+ *   value:  in_a = obs_dim, in_b = 0, n_hidden = 2, head net.4 256 -> 1
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rlx_iql_mlp_layout {
+    int32_t n_nets;       /* 1 or 2 */
+    int32_t in_a;         /* D: columns of xa */
+    int32_t in_b;         /* columns of xb read beside xa by the first layer, or 0 */
+    int32_t n_hidden;     /* 2 or 3 hidden layers of 256, each followed by ReLU */
+    int32_t out_dim;      /* head outputs, 1..32 */
+    int32_t hidden;       /* must be 256 */
+    int64_t n_params;     /* elements of the flat buffer */
+    int64_t off_w[2][4];  /* [net][layer] weight; layer n_hidden is the head [out_dim, 256] */
+    int64_t off_b[2][4];  /* [net][layer] bias */
+    int64_t off_logstd;   /* actor_logstd [out_dim] (n_nets == 1), or -1 */
+    float logstd_lo;      /* logstd = clamp(actor_logstd, lo, hi) */
+    float logstd_hi;
+} rlx_iql_mlp_layout;
+
+/* One update's eight metrics, in the order of the reference's update_step_forward. */
+enum rlx_iql_metric {
+    RLX_IQL_CRITIC_LOSS = 0, RLX_IQL_Q1 = 1, RLX_IQL_Q2 = 2, RLX_IQL_VALUE_LOSS = 3, RLX_IQL_V = 4, RLX_IQL_ACTOR_LOSS = 5,
+    RLX_IQL_ADV_MEAN = 6, RLX_IQL_ADV_STD = 7, RLX_IQL_METRICS = 8
+};
+
+/* Forward (one launch): out [n_nets][m][out_dim].  Rows [0, m_first) come from xa, rows [m_first, m) from xa2 (value(obs) and
+ * value(next_obs) in one launch; xa2 == NULL: m_first == m); xb [m, in_b] or NULL when in_b == 0.  acts [n_nets][n_hidden][m][256]
+ * keeps the post-ReLU activations for a backward, or NULL.  actions [m, out_dim] with logprob [m] (both or neither; needs
+ * off_logstd): the log-prob of those actions under tanh(Normal(out, exp(clamp(actor_logstd)))),
+ *   raw = atanh(clamp(a, -c, c)), c = float32(1 - 1e-6);  lp = sum_j Normal.log_prob(raw_j) - sum_j 2 (log 2 - raw_j - softplus(-2 raw_j)). */
+int rlx_iql_mlp_fwd(const float* params, const rlx_iql_mlp_layout* layout, const float* xa, int64_t m_first, const float* xa2,
+                    const float* xb, int64_t m, float* out, float* acts, const float* actions, float* logprob, rlx_stream_t stream);
+/* Backward from d_out [n_nets][m][out_dim] (three launches) -> grads [slabs][n_params] split-K slabs, every element written
+ * (rlx_clip_adamw_step sums them through grad_partials).  d_logstd [out_dim]: the already reduced gradient of actor_logstd
+ * (rlx_iql_actor_loss), or NULL = zero.  ReLU mask: h > 0.  workspace: rlx_iql_mlp_bwd_workspace_bytes(layout, m) bytes. */
+int rlx_iql_mlp_bwd_slabs(int64_t m);
+size_t rlx_iql_mlp_bwd_workspace_bytes(const rlx_iql_mlp_layout* layout, int64_t m);
+int rlx_iql_mlp_bwd(const float* params, const rlx_iql_mlp_layout* layout, const float* xa, const float* xb, const float* acts,
+                    const float* d_out, const float* d_logstd, int64_t m, float* grads, int slabs, void* workspace,
+                    size_t workspace_bytes, rlx_stream_t stream);
+/* The loss legs: m values each, one workgroup, f64 inside.  metrics: float[RLX_IQL_METRICS], each leg writes its own slots.
+ * value:  q_target [2][m] (the target twin's out) -> q_min = min(q1, q2) [m] (kept for the actor leg), diff = q_min - v,
+ *         w = |expectile - 1[diff < 0]|, VALUE_LOSS = mean(w diff^2), V = mean(v), d_v = -2 w diff / m. */
+int rlx_iql_value_loss(const float* q_target, const float* v, int64_t m, double expectile, float* d_v, float* q_min,
+                       float* metrics, rlx_stream_t stream);
+/* actor:  adv = q_min - new_v, e = min(exp(adv temperature), 100), ACTOR_LOSS = -mean(e logprob), d_lp = -e / m, ADV_MEAN,
+ *         ADV_STD (Bessel's correction: NaN at m == 1, as torch); then through the log-prob, with mean [m, A] the actor's out:
+ *         d_mean = d_lp (raw - mean) / var [m, A] (the d_out of rlx_iql_mlp_bwd) and d_logstd_j = sum_rows d_lp ((raw - mean)^2 / var - 1)
+ *         where lo <= actor_logstd_j <= hi, else 0.  q_min == NULL: d_lp is an INPUT and only the log-prob backward runs. */
+int rlx_iql_actor_loss(const float* params, const rlx_iql_mlp_layout* layout, const float* q_min, const float* new_v,
+                       const float* logprob, const float* mean, const float* actions, int64_t m, double temperature, float* d_lp,
+                       float* d_mean, float* d_logstd, float* metrics, rlx_stream_t stream);
+/* critic: q [2][m], target = rewards + gamma masks next_v, CRITIC_LOSS = mean((q1 - target)^2 + (q2 - target)^2), Q1, Q2 means,
+ *         d_q [2][m] = 2 (q_i - target) / m. */
+int rlx_iql_critic_loss(const float* q, const float* next_v, const float* rewards, const float* masks, int64_t m, double gamma,
+                        float* d_q, float* metrics, rlx_stream_t stream);
+/* target <- target (1 - tau), then target <- target + tau online, each step rounded as torch's _foreach_mul_ / _foreach_add_(alpha). */
+int rlx_soft_update(float* target, const float* online, int64_t n, double tau, rlx_stream_t stream);
 
 #ifdef __cplusplus
 }

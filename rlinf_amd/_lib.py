@@ -95,6 +95,15 @@ class SacQLayout(Structure):  # include/rlx.h: rlx_sac_q_layout
                 ("off_beta", (c_int64 * 3) * 2)]
 
 
+class IqlMlpLayout(Structure):  # include/rlx.h: rlx_iql_mlp_layout
+    _fields_ = [("n_nets", c_int32), ("in_a", c_int32), ("in_b", c_int32), ("n_hidden", c_int32), ("out_dim", c_int32),
+                ("hidden", c_int32), ("n_params", c_int64), ("off_w", (c_int64 * 4) * 2), ("off_b", (c_int64 * 4) * 2),
+                ("off_logstd", c_int64), ("logstd_lo", c_float), ("logstd_hi", c_float)]
+
+
+IQL_METRIC_NAMES = ("critic_loss", "q1", "q2", "value_loss", "v", "actor_loss", "adv_mean", "adv_std")  # include/rlx.h: rlx_iql_metric
+
+
 class AdamwParams(Structure):
     _fields_ = [
         ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
@@ -315,6 +324,17 @@ PROTOTYPES = {
     "rlx_sac_q_bwd_workspace_bytes": (c_size_t, [POINTER(SacQLayout), c_int64]),
     "rlx_sac_q_bwd": (c_int, [c_void_p, POINTER(SacQLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                               c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rlx_iql_mlp_fwd": (c_int, [c_void_p, POINTER(IqlMlpLayout), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
+    "rlx_iql_mlp_bwd_slabs": (c_int, [c_int64]),
+    "rlx_iql_mlp_bwd_workspace_bytes": (c_size_t, [POINTER(IqlMlpLayout), c_int64]),
+    "rlx_iql_mlp_bwd": (c_int, [c_void_p, POINTER(IqlMlpLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                c_int, c_void_p, c_size_t, c_void_p]),
+    "rlx_iql_value_loss": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_iql_actor_loss": (c_int, [c_void_p, POINTER(IqlMlpLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_iql_critic_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p]),
+    "rlx_soft_update": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p]),
 }
 XGMI_HANDLE_BYTES, XGMI_MAX_RANKS = 64, 8
 
@@ -341,11 +361,11 @@ def load() -> ctypes.CDLL:
             raise RlxError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.rlx_version() < 118:
+    if lib.rlx_version() < 119:
         raise RlxError("librlx_hip.so is older than this Python package; rebuild it")
     mirrors = (GaeParams, PpoLossParams, GatherField, AdamwGroup, AdamwParams, MlpLayout, ValueJob, RolloutStep, PpoStepArgs,
                DecoupledLossParams, TokenRows, TokenLossParams, CopySegment)  # the order rlx_abi_struct_sizes documents
-    later = (VersionStats, SegField, SacActorLayout, SacQLayout)  # the order rlx_abi_struct_sizes_ext documents
+    later = (VersionStats, SegField, SacActorLayout, SacQLayout, IqlMlpLayout)  # the order rlx_abi_struct_sizes_ext documents
     for query, classes, which in ((lib.rlx_abi_struct_sizes, mirrors, ""), (lib.rlx_abi_struct_sizes_ext, later, "later ")):
         sizes = (c_size_t * len(classes))()
         if query(ctypes.cast(sizes, c_void_p), len(classes)) != len(classes):

@@ -332,6 +332,86 @@ def validate_rollout_store_cfg(alg) -> None:
             "algorithm.loss_type must be 'decoupled_actor_critic'")
 
 
+def validate_offline_cfg(cfg):
+    """rlinf/config.py:1184-1278 (offline tasks: IQL) with the reference's checks and messages, then this build's own limits,
+    each refused by name: the HIP learner is one process, 256 wide, without dropout, with a state-independent log-std and one
+    action chunk.  ``use_fsdp_wrap``, ``offline_torch_compile`` and ``offline_compile_mode`` are accepted and have no effect at
+    world size 1.  Evaluation environments are not part of this path."""
+    actor_global = cfg.actor.get("global_batch_size", None)
+    actor_micro = cfg.actor.get("micro_batch_size", None)
+    runner_local_update_steps = cfg.runner.get("local_update_steps", None)
+    runner_max_steps = cfg.runner.get("max_steps", None)
+    runner_only_eval = cfg.runner.get("only_eval", None)
+    algorithm_gamma = cfg.algorithm.get("gamma", None)
+    actor_seed = cfg.actor.get("seed", None)
+    for value, name in ((actor_global, "actor.global_batch_size"), (actor_micro, "actor.micro_batch_size"),
+                        (runner_local_update_steps, "runner.local_update_steps"), (runner_max_steps, "runner.max_steps"),
+                        (runner_only_eval, "runner.only_eval"), (algorithm_gamma, "algorithm.gamma"), (actor_seed, "actor.seed")):
+        if value is None:
+            raise AssertionError(f"offline training requires {name}")
+    actor_global_int, actor_micro_int = int(actor_global), int(actor_micro)
+    try:
+        float(algorithm_gamma)
+    except (TypeError, ValueError) as exc:
+        raise AssertionError(f"algorithm.gamma must be numeric, got {algorithm_gamma!r}") from exc
+    try:
+        int(actor_seed)
+    except (TypeError, ValueError) as exc:
+        raise AssertionError(f"actor.seed must be int-castable, got {actor_seed!r}") from exc
+    assert actor_global_int > 0, f"actor.global_batch_size must be > 0, got {actor_global_int}"
+    assert actor_micro_int > 0, f"actor.micro_batch_size must be > 0, got {actor_micro_int}"
+    assert int(runner_local_update_steps) > 0, "runner.local_update_steps must be > 0 for offline training"
+    assert int(runner_max_steps) >= 0, f"runner.max_steps must be >= 0, got {int(runner_max_steps)}"
+    assert actor_global_int >= actor_micro_int, "actor.global_batch_size must be >= actor.micro_batch_size for offline training"
+    cfg.runner.only_eval = bool(runner_only_eval)
+
+    # ---- this build's limits ----
+    alg, model_cfg = cfg.algorithm, cfg.actor.get("model", None) or DictConfig({})
+    world = _placement_world_size(cfg, "actor")
+    if world > 1:
+        raise ValueError(f"actor world size {world} is not supported: the HIP IQL learner is one process (world size 1)")
+    if actor_micro_int != actor_global_int:
+        raise ValueError("actor.micro_batch_size must equal per-rank batch size (actor.global_batch_size // world_size); got "
+                         f"micro_batch_size={actor_micro}, expected {actor_global_int}.")
+    if "dropout_rate" in alg and alg["dropout_rate"] is not None:
+        raise ValueError(f"algorithm.dropout_rate={alg['dropout_rate']} is not supported: the HIP IQL networks have no dropout (null)")
+    hidden = alg.get("hidden_dims", None)
+    if hidden is None:
+        raise ValueError("algorithm.hidden_dims is required for IQL offline training.")
+    if list(hidden) != [256, 256]:
+        raise ValueError(f"algorithm.hidden_dims={list(hidden)} is not supported: the HIP IQL networks are [256, 256]")
+    if model_cfg.get("num_action_chunks", None) is None:
+        raise ValueError("actor.model.num_action_chunks is required for IQL offline training.")
+    if int(model_cfg.num_action_chunks) != 1:
+        raise ValueError(f"actor.model.num_action_chunks={model_cfg.num_action_chunks} is not supported: offline IQL on HIP needs "
+                         "num_action_chunks == 1")
+    ic = model_cfg.get("iql_config", None)
+    if ic is None:
+        raise ValueError("actor.model.iql_config is required for IQL actor.")
+    missing = [k for k in ("hidden_dims", "dropout_rate", "state_dependent_std", "log_std_min", "log_std_max") if k not in ic]
+    if missing:
+        raise ValueError(f"actor.model.iql_config missing required keys: {missing}")
+    if bool(ic["state_dependent_std"]):
+        raise ValueError("actor.model.iql_config.state_dependent_std=true is not supported: the HIP actor has the state-independent "
+                         "actor_logstd parameter")
+    if ic["dropout_rate"] is not None:
+        raise ValueError(f"actor.model.iql_config.dropout_rate={ic['dropout_rate']} is not supported: the HIP IQL networks have no "
+                         "dropout (null)")
+    if list(ic["hidden_dims"]) != [256, 256]:
+        raise ValueError(f"actor.model.iql_config.hidden_dims={list(ic['hidden_dims'])} is not supported: the HIP IQL networks are "
+                         "[256, 256]")
+    for key, hi in (("obs_dim", 64), ("action_dim", 32)):  # optional here: the data set gives them; checked again when it is read
+        v = model_cfg.get(key, None)
+        if v is not None and not 1 <= int(v) <= hi:
+            raise ValueError(f"actor.model.{key}={v} out of range [1, {hi}]")
+    precision = str(model_cfg.get("precision", "32"))
+    if precision not in ("32", "fp32", "float32"):
+        raise ValueError(f"actor.model.precision={precision!r} is not supported: the HIP IQL networks are float32")
+    for name in ("optim", "critic_optim", "value_optim"):
+        assert cfg.actor.get(name, None) is not None, f"actor.{name} is required for IQL offline training"
+    return cfg
+
+
 def validate_cfg(cfg) -> DictConfig:
     """Fill defaults and assert consistency; returns the config (rlinf/config.py:1455-1566)."""
     if not isinstance(cfg, DictConfig):
@@ -346,6 +426,8 @@ def validate_cfg(cfg) -> DictConfig:
         cfg.cluster = DictConfig({"num_nodes": 1, "component_placement": {"env,rollout,actor": "all"}})
     cfg.runner.save_interval = cfg.runner.get("save_interval", -1)
     task = cfg.runner.get("task_type", None)
+    if task == "offline":  # rlinf/config.py:1516-1517
+        return validate_offline_cfg(cfg)
     assert task in ("embodied",), f"task_type {task!r} is not served by this build (embodied only)"
     alg = cfg.algorithm
     alg.adv_type = alg.get("adv_type", "gae")

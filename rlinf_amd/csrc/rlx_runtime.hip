@@ -47,7 +47,7 @@ extern "C" int rlx_abi_struct_sizes(size_t* sizes, int n) {
 
 extern "C" int rlx_abi_struct_sizes_ext(size_t* sizes, int n) {
     const size_t all[] = {sizeof(rlx_version_stats_out), sizeof(rlx_seg_field), sizeof(rlx_sac_actor_layout),
-                          sizeof(rlx_sac_q_layout)};
+                          sizeof(rlx_sac_q_layout), sizeof(rlx_iql_mlp_layout)};
     const int count = (int)(sizeof(all) / sizeof(all[0]));
     for (int i = 0; sizes != nullptr && i < n && i < count; ++i) sizes[i] = all[i];
     return count;

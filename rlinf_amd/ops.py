@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (AdamwGroup, AdamwParams, GaeParams, GatherField, MlpLayout, PpoLossParams, PpoStepArgs, RlxError,
+from ._lib import (AdamwGroup, AdamwParams, GaeParams, GatherField, IqlMlpLayout, MlpLayout, PpoLossParams, PpoStepArgs, RlxError,
                    RolloutStep, SacActorLayout, SacQLayout)
 
 
@@ -1036,6 +1036,122 @@ def sac_q_bwd(params, layout: SacQLayout, states, actions, acts, rstd, d_q, want
     _lib.launch("rlx_sac_q_bwd", dev, params, layout, states, actions, acts, rstd, _as_f32(d_q, "d_q"), M, grads, slabs, d_actions,
                 workspace, workspace.numel())
     return grads, d_actions
+
+
+# --------------------------------------------------------------------------------------------
+# offline IQL for the MLP policy: networks, loss legs, target update (iql_mlp.hip)
+# --------------------------------------------------------------------------------------------
+def _rows(t, width: int, name: str):
+    t = _as_f32(t, name)
+    if t.dim() != 2 or t.shape[1] != width:
+        raise RlxError(f"{name} must be [M, {width}], got {tuple(t.shape)}")
+    return t
+
+
+def _f32_vec(t, n: int, name: str):
+    t = _as_f32(t, name)
+    if t.numel() != n:
+        raise RlxError(f"{name} must hold {n} elements, got {tuple(t.shape)}")
+    return t
+
+
+def iql_mlp_fwd(params, layout: IqlMlpLayout, xa, xb=None, xa2=None, train: bool = False, actions=None):
+    """-> (out [n_nets, M, out_dim], acts [n_nets, n_hidden, M, 256] | None, logprob [M] | None).  ``xa2``: further rows behind
+    ``xa``'s in the same launch; ``actions`` [M, out_dim]: the actor's log-prob of them; ``train`` keeps what backward needs."""
+    dev = _dev(params, xa, xb, xa2, actions)
+    a1 = _rows(xa, layout.in_a, "xa")
+    a2 = _rows(xa2, layout.in_a, "xa2") if xa2 is not None else None
+    M = a1.shape[0] + (a2.shape[0] if a2 is not None else 0)
+    b = _rows(xb, layout.in_b, "xb") if xb is not None else None
+    ac = _rows(actions, layout.out_dim, "actions") if actions is not None else None
+    for t, name in ((b, "xb"), (ac, "actions")):
+        if t is not None and t.shape[0] != M:
+            raise RlxError(f"{name} must have {M} rows, got {t.shape[0]}")
+    out = torch.empty((layout.n_nets, M, layout.out_dim), dtype=torch.float32, device=dev)
+    acts = torch.empty((layout.n_nets, layout.n_hidden, M, 256), dtype=torch.float32, device=dev) if train else None
+    logprob = torch.empty((M,), dtype=torch.float32, device=dev) if ac is not None else None
+    _lib.launch("rlx_iql_mlp_fwd", dev, _as_f32(params, "params"), layout, a1, a1.shape[0], a2, b, M, out, acts, ac, logprob)
+    return out, acts, logprob
+
+
+def iql_mlp_bwd(params, layout: IqlMlpLayout, xa, xb, acts, d_out, d_logstd=None, grads=None, workspace=None):
+    """-> grads [slabs, n_params] (split-K slabs; every element written)."""
+    lib = _lib.load()
+    dev = _dev(params, xa, xb, acts, d_out, d_logstd)
+    a1 = _rows(xa, layout.in_a, "xa")
+    M = a1.shape[0]
+    b = _rows(xb, layout.in_b, "xb") if xb is not None else None
+    do = _f32_vec(d_out, layout.n_nets * M * layout.out_dim, "d_out")
+    ac = _f32_vec(acts, layout.n_nets * layout.n_hidden * M * 256, "acts")
+    dl = _f32_vec(d_logstd, layout.out_dim, "d_logstd") if d_logstd is not None else None
+    slabs = lib.rlx_iql_mlp_bwd_slabs(M) if grads is None else grads.shape[0]
+    if grads is None:
+        grads = torch.empty((slabs, layout.n_params), dtype=torch.float32, device=dev)
+    ws_bytes = lib.rlx_iql_mlp_bwd_workspace_bytes(byref(layout), M)
+    if workspace is None or workspace.numel() < ws_bytes:
+        workspace = _lib.workspace(dev, ws_bytes)
+    _lib.launch("rlx_iql_mlp_bwd", dev, _as_f32(params, "params"), layout, a1, b, ac, do, dl, M, grads, slabs, workspace,
+                workspace.numel())
+    return grads
+
+
+def iql_value_loss(q_target, v, expectile: float, metrics):
+    """q_target [2, M] (the target twin's out), v [M] -> (d_v [M], q_min [M]); metrics[value_loss, v] written."""
+    dev = _dev(q_target, v, metrics)
+    M = v.numel()
+    qt, vv, mt = _f32_vec(q_target, 2 * M, "q_target"), _as_f32(v, "v"), _f32_vec(metrics, 8, "metrics")
+    d_v, q_min = torch.empty((M,), dtype=torch.float32, device=dev), torch.empty((M,), dtype=torch.float32, device=dev)
+    _lib.launch("rlx_iql_value_loss", dev, qt, vv, M, float(expectile), d_v, q_min, mt)
+    return d_v, q_min
+
+
+def iql_actor_loss(params, layout: IqlMlpLayout, q_min, new_v, logprob, mean, actions, temperature: float, metrics):
+    """-> (d_mean [M, A], d_logstd [A], d_lp [M]); metrics[actor_loss, adv_mean, adv_std] written."""
+    dev = _dev(params, q_min, new_v, logprob, mean, actions, metrics)
+    M, A = logprob.numel(), layout.out_dim
+    qm, nv, lp = _f32_vec(q_min, M, "q_min"), _f32_vec(new_v, M, "new_v"), _as_f32(logprob, "logprob")
+    mu, ac, mt = _f32_vec(mean, M * A, "mean"), _f32_vec(actions, M * A, "actions"), _f32_vec(metrics, 8, "metrics")
+    d_lp = torch.empty((M,), dtype=torch.float32, device=dev)
+    d_mean = torch.empty((M, A), dtype=torch.float32, device=dev)
+    d_logstd = torch.empty((A,), dtype=torch.float32, device=dev)
+    _lib.launch("rlx_iql_actor_loss", dev, _as_f32(params, "params"), layout, qm, nv, lp, mu, ac, M, float(temperature), d_lp, d_mean,
+                d_logstd, mt)
+    return d_mean, d_logstd, d_lp
+
+
+def iql_logprob_bwd(params, layout: IqlMlpLayout, mean, actions, d_lp):
+    """The actor's log-prob backward alone, from a given d_lp [M] -> (d_mean [M, A], d_logstd [A])."""
+    dev = _dev(params, mean, actions, d_lp)
+    M, A = d_lp.numel(), layout.out_dim
+    mu, ac, dl = _f32_vec(mean, M * A, "mean"), _f32_vec(actions, M * A, "actions"), _as_f32(d_lp, "d_lp")
+    d_mean = torch.empty((M, A), dtype=torch.float32, device=dev)
+    d_logstd = torch.empty((A,), dtype=torch.float32, device=dev)
+    _lib.launch("rlx_iql_actor_loss", dev, _as_f32(params, "params"), layout, None, None, None, mu, ac, M, 1.0, dl, d_mean, d_logstd,
+                None)
+    return d_mean, d_logstd
+
+
+def iql_critic_loss(q, next_v, rewards, masks, gamma: float, metrics):
+    """q [2, M] -> d_q [2, M]; metrics[critic_loss, q1, q2] written."""
+    dev = _dev(q, next_v, rewards, masks, metrics)
+    M = next_v.numel()
+    qq, nv, mt = _f32_vec(q, 2 * M, "q"), _as_f32(next_v, "next_v"), _f32_vec(metrics, 8, "metrics")
+    r, mk = _f32_vec(rewards, M, "rewards"), _f32_vec(masks, M, "masks")
+    d_q = torch.empty((2, M), dtype=torch.float32, device=dev)
+    _lib.launch("rlx_iql_critic_loss", dev, qq, nv, r, mk, M, float(gamma), d_q, mt)
+    return d_q
+
+
+def soft_update_(target, online, tau: float):
+    """target <- target * (1 - tau); target <- target + tau * online, over flat f32 buffers, in place."""
+    dev = _dev(target, online)
+    for t in (target, online):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RlxError("soft_update_ needs contiguous float32 buffers")
+    if target.numel() != online.numel():
+        raise RlxError("buffer sizes do not match")
+    _lib.launch("rlx_soft_update", dev, target, online, target.numel(), float(tau))
+    return target
 
 
 # --------------------------------------------------------------------------------------------
